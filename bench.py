@@ -2,7 +2,15 @@
 """bench.py -- device-resident checksummed GiB/s on MI355X (BASELINE.json metric).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config <one of the configs below>]
+                   [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node N ... bench.py --gpus N      (one rank per GPU)
+
+A plain run sets up, warms up, times the K steps and prints the result line (the headline value,
+`ms_per_step`, and the roofline figures the timed region's own HIP events give).  `--full` adds
+the legs that take runs of their own: `verified`, `cpu_baseline`, `e2e_host_to_host` and the
+reassembly's `copy_ceiling` (each still switched off by its --no-* option).  `--dump-outputs DIR`
+writes what the last timed step returned as DIR/<name>.npy (float32); the inputs are seeded, so
+two builds run with the same arguments can be compared output for output.
 
 A step = one pass of the hot path over one batch resident in HBM:
   c1 (default, the metric's config): 256K x 1500 B frames, raw pico_checksum per frame
@@ -26,8 +34,8 @@ c1/c2/c3 are weak-scaled: every rank checksums its own batch of that size (frame
 are independent shards; no collective touches the data path -- RCCL only carries the
 barrier and the max-over-ranks timing).
 
-Rank 0 prints ONE JSON line.  `verified` checks the outputs of the timed region against the CPU
-oracle (every frame of the uniform configs, every datagram of the fused ones); any mismatch
+Rank 0 prints ONE JSON line.  `verified` (--full) checks the outputs of the timed region against the
+CPU oracle (every frame of the uniform configs, every datagram of the fused ones); any mismatch
 makes the run exit non-zero.  `value` = the bytes of all ranks / the max over ranks of each
 rank's timed region (from a common start barrier to its own device synchronize; the closing
 barrier is outside it).  `roofline` is the checksum kernel's achieved algorithmic HBM
@@ -35,7 +43,7 @@ bandwidth (HIP events bracketing the K timed launches on the launch stream; elap
 average launch duration) against the 8.0 TB/s HBM3E peak; `traffic` is the PMC-measured HBM bytes per launch
 from profiles/pmc_traffic.json (FETCH_SIZE x2, calibrated to 128 B per touched line by tools/fetch_calib.py,
 + WRITE_SIZE; separate rocprofv3 passes recorded earlier, named in `traffic_source`) when recorded for this config;
-`cpu_baseline` times the reference's own pico_checksum (compiled from stack/pico_frame.c,
+`cpu_baseline` (--full) times the reference's own pico_checksum (compiled from stack/pico_frame.c,
 oracle/_ref) on the host cores over a bounded sample of the same frames.
 """
 from __future__ import annotations
@@ -138,6 +146,11 @@ def parse():
     p.add_argument("--steps", type=int, default=200)
     p.add_argument("--warmup", type=int, default=20)
     p.add_argument("--config", default="c1", choices=sorted(CONFIGS))
+    p.add_argument("--full", action="store_true",
+                   help="also run the legs beside the headline figure: the parity check of the timed outputs, "
+                        "the CPU baseline, the host-to-host paths and the reassembly's copy ceiling")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="write what the last timed step returned as DIR/<name>.npy (float32)")
     p.add_argument("--rotate", type=int, default=0, help="rotating batch copies (0 = enough for >= 1 GiB)")
     p.add_argument("--cpu-seconds", type=float, default=4.0, help="target CPU-baseline wall per leg")
     p.add_argument("--no-cpu", action="store_true")
@@ -755,6 +768,47 @@ def load_traffic(config: str):
         return None, None
 
 
+DUMP_SAMPLE = 1 << 22        # bytes sampled of a buffer the timed path writes (16 MiB as float32)
+
+
+def sample_bytes(buf: torch.Tensor, idx: np.ndarray) -> np.ndarray:
+    """buf[idx] as float32: a fixed sample of a byte buffer too large to dump whole."""
+    return buf[torch.from_numpy(idx).to(buf.device)].cpu().numpy().astype(np.float32)
+
+
+def dump_outputs(path: str, rank: int, cfg: dict, slot, out) -> None:
+    """--dump-outputs: what the last timed step handed its caller, one float32 .npy per array (every
+    value is an integer below 2^24, exact in float32).  The result arrays whole; of the bytes the
+    step wrote in place (TX crc fields, NAT rewrites) or gathered (the reassembled datagrams) a
+    fixed, seeded sample of DUMP_SAMPLE positions.  Ranks past 0 add `.rank<r>` to the name."""
+    os.makedirs(path, exist_ok=True)
+    kind = cfg["kind"]
+    g = np.random.default_rng(2024)
+    arrays = {}
+    if kind == "uniform":
+        arrays["checksum"] = out.cpu().numpy().view(np.uint16)
+    elif kind == "frag":
+        b, d, gr, o, od, nfr, payload = slot
+        arrays["length"] = out[0].cpu().numpy().view(np.uint32)
+        arrays["transport_checksum"] = out[1].cpu().numpy().view(np.uint16)
+        arrays["verdict"] = out[2].cpu().numpy()
+        # bytes of the reassembled datagrams (header + transport; the gaps between them are never written)
+        odh = od.cpu().numpy().view(batch.DESC_DTYPE)
+        n = odh.size
+        span = (40 if cfg.get("v6") else 20) + payload // n
+        idx = odh["off"].astype(np.int64)[g.integers(0, n, DUMP_SAMPLE)] + g.integers(0, span, DUMP_SAMPLE)
+        arrays["reassembled_sample"] = sample_bytes(o, idx)
+    else:
+        names = ("transport_checksum", "verdict") if kind == "ipv6" else ("net_checksum", "transport_checksum", "verdict")
+        for name, x in zip(names, out):
+            x = x.cpu().numpy()
+            arrays[name] = x.view(np.uint16) if x.dtype == np.int16 else x
+        if cfg.get("nat") or (cfg.get("tx") and cfg.get("write", True)):
+            arrays["frames_sample"] = sample_bytes(slot[0], g.integers(0, slot[0].numel(), DUMP_SAMPLE))
+    for name, x in arrays.items():
+        np.save(os.path.join(path, f"{name}{f'.rank{rank}' if rank else ''}.npy"), x.astype(np.float32))
+
+
 def _free_port() -> int:
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -790,6 +844,8 @@ def launch_ranks(a) -> None:
 
 def main():
     a = parse()
+    if not a.full:                 # a plain run: the timed steps and the result line, none of the other legs
+        a.no_cpu = a.no_e2e = a.no_verify = True
     launch_ranks(a)
     if os.environ.get("PICO_BENCH_DRY") == "1":      # launcher test (tests/test_bench_launch.py): no GPU use
         print(json.dumps({"rank": int(os.environ.get("RANK", 0)), "world": int(os.environ.get("WORLD_SIZE", 1)),
@@ -978,6 +1034,13 @@ def main():
     achieved = algo_bytes / (kern_ms / 1e3) / 1e9
     traffic, traffic_src = load_traffic(a.config)
 
+    if a.dump_outputs:                                   # the last timed step's rotation slot
+        last = (a.steps - 1) % rot
+        if cfg["kind"] == "uniform":
+            dump_outputs(a.dump_outputs, rank, cfg, None, outs[last])
+        else:
+            dump_outputs(a.dump_outputs, rank, cfg, sets[last], res[last] if cfg["kind"] == "frag" else outs[last])
+
     # ---- parity of what the timed region produced (every rank checks its own slot 0)
     ver = None
     if not a.no_verify:
@@ -1035,7 +1098,8 @@ def main():
     elif rank == 0 and world == 1 and cfg["kind"] == "frag":
         if not a.no_cpu:
             out["cpu_baseline"] = cpu_baseline_frag(sets[0], a.cpu_seconds / 2, bool(cfg.get("v6")))
-        out["roofline"]["copy_ceiling"] = copy_ceiling(sets[0][6], dev)
+        if a.full:
+            out["roofline"]["copy_ceiling"] = copy_ceiling(sets[0][6], dev)
     if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -15,7 +15,7 @@ for r in $(seq ${ROUNDS:-3}); do
     lib=$R/picotcp_amd/libpicocsum.so
     [ $v != new ] && lib=$R/ablib/libpicocsum_$v.so
     for c in ${CFGS:-c2 c2v6 c2eth c2tx}; do
-      PICO_CSUM_LIB=$lib timeout -k 10 120 python bench.py --config $c --steps ${STEPS:-100} --warmup 10 \
+      PICO_CSUM_LIB=$lib timeout -k 10 120 python bench.py --config $c --steps ${STEPS:-100} --warmup 10 --full \
           --no-e2e --no-cpu ${VERIFY:---no-verify} ${EXTRA:-} > $O/ab_line.json 2> $O/ab_err.txt
       python -c "
 import json; d=json.load(open('$O/ab_line.json')); r=d['roofline']

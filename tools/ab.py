@@ -46,7 +46,7 @@ def main() -> None:
                     else:
                         env.pop("PICO_CSUM_LIB", None)
                     cmd = ["timeout", "-k", "10", "180", sys.executable, os.path.join(ROOT, "bench.py"),
-                           "--config", cfg, "--steps", str(a.steps), "--warmup", "10", "--no-cpu", "--no-e2e"]
+                           "--config", cfg, "--steps", str(a.steps), "--warmup", "10", "--full", "--no-cpu", "--no-e2e"]
                     if not a.verify:
                         cmd.append("--no-verify")
                     p = subprocess.run(cmd + extra, env=env, capture_output=True, text=True)
