@@ -46,6 +46,13 @@ __device__ uint32_t g_stamps_n;
 constexpr uint32_t WPB = 4;
 constexpr uint32_t HW = 8;   // head-window chunks the fused modes load in phase 1 (temporal loads:
                              // non-temporal ones measured 5 % slower, profiles/r02nt)
+// The rounds' product shape (measured): 8 chunks per lane per round, non-temporal
+// loads in the >= 16-lane rounds, the 1-lane class for frames of <= 8 chunks.  CPL 8 keeps 8 KiB
+// of loads in flight per wave within 128 VGPRs (4 waves per SIMD: a 256K-frame batch at 64 frames
+// per wave is one residency round); CPL 4 fits 64 VGPRs (8 waves per SIMD).
+constexpr int CPL = 8;
+constexpr bool NT = true;
+constexpr bool SMALL = true;
 
 struct SortedWaveLds {
     uint32_t acc_all[64];
@@ -67,9 +74,6 @@ struct SortedWaveLds {
 // (profiles/r03s3/README.md): 8 chunks per lane per step (8 KiB; StreamLds 10 KiB a wave, 4
 // workgroups of 4 waves per CU), two steps in flight, non-temporal loads.
 constexpr uint32_t SCPL = 8;                 // chunks per lane per step
-#ifndef STREAM_LAST_NOPF
-#define STREAM_LAST_NOPF 1
-#endif
 constexpr uint32_t SQ = 64u * SCPL;          // chunks per step
 struct StreamLds {
     uint4 raw[SQ];           // the step's bytes, chunk slots swizzled (sslot)
@@ -89,7 +93,7 @@ union SortedWaveSmem<false> {
 };
 
 // One round: group g sums the frame at position pos + g of the class order.
-template <int G, int CPL, bool PERM, bool NT, bool XO>
+template <int G, bool PERM, bool NTL, bool XO>
 __device__ __forceinline__ void sorted_round(const RawArgs& p, SortedWaveLds& L, uint32_t pos, uint32_t m) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t g = lane / G, l = lane % G;
@@ -111,7 +115,7 @@ __device__ __forceinline__ void sorted_round(const RawArgs& p, SortedWaveLds& L,
 #pragma unroll
         for (int c = 0; c < CPL; ++c) {
             const uint32_t k = kb + l + G * c;
-            v[c] = k < nch ? load_chunk_t<NT>(a0, k) : make_uint4(0, 0, 0, 0);
+            v[c] = k < nch ? load_chunk_t<NTL>(a0, k) : make_uint4(0, 0, 0, 0);
         }
         // interior chunks unmasked; masked sums only where a chunk holds a region edge
         // (a wave-uniform branch: skipped for slots no lane's edge falls in)
@@ -149,27 +153,27 @@ __device__ __forceinline__ void sorted_round(const RawArgs& p, SortedWaveLds& L,
 // SMALL adds a 1-lane class below the 4-lane one: frames of <= CPL chunks (<= 8 x 16 B,
 // e.g. 64-byte IMIX frames) are summed one frame per lane, 64 per round, so a wave
 // pays one dependent HBM round trip for all its small frames instead of one per 16.
-template <int CPL, bool PERM, bool NT, bool XO, bool SMALL>
+template <bool PERM, bool XO>
 __device__ __forceinline__ void sorted_rounds(const RawArgs& p, SortedWaveLds& L, const uint32_t (&e)[5], uint32_t m) {
     // position s holds a frame of class <= c iff s < e[c]; a round of width G may
     // take the next 64/G positions when the last of them is of class <= G's class
     constexpr int o = SMALL ? 1 : 0;
     uint32_t pos = 0;
     if constexpr (SMALL) {
-        if (e[0]) { sorted_round<1, CPL, PERM, false, XO>(p, L, 0u, min(m, e[0])); pos = min(e[0], 64u); }
+        if (e[0]) { sorted_round<1, PERM, false, XO>(p, L, 0u, min(m, e[0])); pos = min(e[0], 64u); }
     }
     while (pos < m) {
-        if (min(pos + 15u, m - 1u) < e[o])            { sorted_round<4, CPL, PERM, false, XO>(p, L, pos, m);  pos += 16u; }
-        else if (min(pos + 7u, m - 1u) < e[o + 1])    { sorted_round<8, CPL, PERM, false, XO>(p, L, pos, m);  pos += 8u; }
-        else if (min(pos + 3u, m - 1u) < e[o + 2])   { sorted_round<16, CPL, PERM, NT, XO>(p, L, pos, m); pos += 4u; }
-        else if (min(pos + 1u, m - 1u) < e[o + 3])   { sorted_round<32, CPL, PERM, NT, XO>(p, L, pos, m); pos += 2u; }
-        else                                          { sorted_round<64, CPL, PERM, NT, XO>(p, L, pos, m); pos += 1u; }
+        if (min(pos + 15u, m - 1u) < e[o])            { sorted_round<4, PERM, false, XO>(p, L, pos, m);  pos += 16u; }
+        else if (min(pos + 7u, m - 1u) < e[o + 1])    { sorted_round<8, PERM, false, XO>(p, L, pos, m);  pos += 8u; }
+        else if (min(pos + 3u, m - 1u) < e[o + 2])   { sorted_round<16, PERM, NT, XO>(p, L, pos, m); pos += 4u; }
+        else if (min(pos + 1u, m - 1u) < e[o + 3])   { sorted_round<32, PERM, NT, XO>(p, L, pos, m); pos += 2u; }
+        else                                          { sorted_round<64, PERM, NT, XO>(p, L, pos, m); pos += 1u; }
     }
 }
 
 // MODE: 0 RAW (p.crc_off / p.flags / p.out / p.bad), 1 fused IPv4, 2 fused IPv6,
-// 3 Ethernet front end (per frame: destination filter, ethertype -> IPv4 / IPv6 / ARP / drop;
-// pico_ethernet.c:180-235) -- IPv4 / IPv6 outputs in the out_net / out_l4 / verdict fields of FlatArgs.
+// 3 Ethernet front end (per frame: destination filter, ethertype -> IPv4 / IPv6 / ARP / drop:
+// eth_classify) -- IPv4 / IPv6 outputs in the out_net / out_l4 / verdict fields of FlatArgs.
 // Phase 4: lane `lane` finalizes its frame (output index idx) from the LDS state.
 template <int MODE>
 __device__ __forceinline__ void finish_frame(const FlatArgs& p, uint64_t idx, bool tx, uint32_t acc_all,
@@ -320,10 +324,150 @@ __device__ __forceinline__ void window_words(const uint4 (&hw)[HW], uint32_t pos
     for (int m = 0; m < NW; ++m) H[m] = __builtin_amdgcn_alignbyte(E[m + 1], E[m], sh);
 }
 
-// CPL 8 keeps 8 KiB of loads in flight per wave within 128 VGPRs (4 waves per
-// SIMD: a 256K-frame batch at 64 frames per wave is one residency round); CPL 4
-// fits 64 VGPRs (8 waves per SIMD).
-template <int MODE, bool NT, int CPL, bool SMALL>
+// ---------------------------------------------------------------- the protocols' header rules
+//
+// One statement of each rule for both paths (sorted_batch's phase 1 and the stream's finish): pure
+// functions of header words (little-endian dwords, as window_words / lds_words give them) and
+// scalars.  Region bookkeeping (span, ext, xpos, prefixes) stays with the callers.
+
+// pico_ethernet_receive / pico_eth_receive (pico_ethernet.c:180-235): the destination filter (own
+// MAC, 01:00:5e, 33:33, broadcast; RX with F_MACF only), then the ethertype (m0, m1: destination
+// bytes 0-3, 4-5; et: bytes 12-13) -> l2v 0 / V_DROP_L2 / V_ARP and the family 0 / 4 / 6.
+struct EthClass {
+    uint32_t l2v, fam;
+};
+[[maybe_unused]] __device__ __forceinline__ EthClass eth_classify(uint32_t m0, uint32_t m1, uint32_t et,
+                                                                  uint32_t flags, bool tx, uint32_t mac_lo,
+                                                                  uint32_t mac_hi) {
+    m1 &= 0xFFFFu;
+    et &= 0xFFFFu;                                         // the ethertype as a little-endian word
+    const bool mine = !(flags & F_MACF) || tx || (m0 == mac_lo && m1 == mac_hi) || (m0 & 0xFFFFFFu) == 0x5E0001u ||
+                      (m0 & 0xFFFFu) == 0x3333u || (m0 == 0xFFFFFFFFu && m1 == 0xFFFFu);
+    if (!mine) return {V_DROP_L2, 0u};
+    if (et == 0x0608u) return {V_ARP, 0u};                 // 0x0806 -> pico_arp_receive
+    if (et == 0x0008u) return {0u, 4u};                    // 0x0800
+    if (et == 0xDD86u) return {0u, 6u};                    // 0x86DD
+    return {V_DROP_L2, 0u};
+}
+// IS_IPV4 / IS_IPV6 (pico_ethernet.c:145,164) on the first IP byte b0 of a frame with a family;
+// ip_len = the bytes behind the Ethernet header (none: no byte to read, MALFORMED)
+[[maybe_unused]] __device__ __forceinline__ EthClass eth_version(EthClass c, uint32_t ip_len, uint32_t b0) {
+    if (c.fam == 0u || ip_len == 0u) return {c.l2v, 0u};
+    if ((b0 & 0xF0u) != (c.fam << 4)) return {V_DROP_L2, 0u};
+    return c;
+}
+
+// pico_ipv4_process_in (pico_ipv4.c:381-456) on the header's five words, avail >= 20 bytes at the
+// header: IHL / total length (uint16 wrap, :395) / max_allowed (:386); the header and pseudo-header
+// sums; after the header check (finish_frame): pico_ipv4_is_valid_src (:425-428, :187-229 --
+// 255.255.255.255, 224-254.x.x.x, 127/8 from a device that is not "loop"), the evil bit
+// (:431-435), IHL < 5 (:438-443): PV_DROP; MF or an offset (:446-455): PV_FRAG, handed to
+// reassembly -- then only the header is summed.  The transport dispatch: RX TCP and UDP (a UDP crc
+// field past the frame: PV_DROP); TX TCP and ICMP, or with nat (F_NAT: pico_nat.c:443-449,
+// :461-465, :511-517, :527-532) TCP and UDP recomputed in full, ICMP only its header checksum --
+// a TX transport shorter than its header: MALFORMED.  xoff: the crc field in the transport (NONE:
+// no field is read).  hl / tl / proto / ipcrc are set whatever the length checks say (they go
+// into fin).
+struct Ip4 {
+    uint32_t hl, tl, proto, ipcrc, pseudo, hdr20, post, verdict, xoff;
+    bool parsed, l4_needed;
+};
+[[maybe_unused]] __device__ __forceinline__ Ip4 ipv4_classify(const uint32_t (&H)[5], uint32_t avail, bool tx,
+                                                              bool nat) {
+    Ip4 c{};
+    c.verdict = V_MALFORMED;
+    c.xoff = NONE;
+    const uint32_t ihl = H[0] & 0x0Fu;
+    c.hl = 20u + (ihl > 5u ? 4u * (ihl - 5u) : 0u);
+    const uint32_t tot = (((H[0] >> 16) & 0xFFu) << 8) | (H[0] >> 24);
+    c.proto = (H[2] >> 8) & 0xFFu;
+    c.ipcrc = H[2] >> 16;
+    c.tl = (tot - c.hl) & 0xFFFFu;
+    const uint32_t max_allowed = (avail - 20u) & 0xFFFFu;
+    if (c.hl > avail || (!tx && c.tl > max_allowed) || c.hl + c.tl > avail) return c;
+    c.parsed = true;
+    c.verdict = 0;
+#pragma unroll
+    for (int m = 0; m < 5; ++m) c.hdr20 = dot2_add(H[m], c.hdr20);
+    c.pseudo = (H[3] & 0xFFFFu) + (H[3] >> 16) + (H[4] & 0xFFFFu) + (H[4] >> 16) + (c.proto << 8) +
+               (((c.tl & 0xFFu) << 8) | (c.tl >> 8));
+    const uint32_t frag = ((H[1] >> 8) & 0xFF00u) | (H[1] >> 24);
+    const uint32_t s0 = H[3] & 0xFFu;
+    const bool bad_src = H[3] == 0xFFFFFFFFu || (s0 != 0xFFu && (s0 & 0xE0u) == 0xE0u) || s0 == 0x7Fu;
+    if (!tx && (bad_src || (frag & 0x8000u) || ihl < 5u)) c.post = PV_DROP;
+    else if (frag & 0x3FFFu) c.post = PV_FRAG;
+    if (c.post) return c;
+    if (!tx) {
+        if (c.proto == 6u) {
+            c.l4_needed = true;
+        } else if (c.proto == 17u) {
+            if (c.hl + 8u > avail) c.post = PV_DROP;
+            else { c.l4_needed = true; c.xoff = 6u; }
+        }
+    } else {
+        const uint32_t need = c.proto == 6u ? 20u : 8u;
+        const uint32_t x = c.proto == 6u ? 16u : c.proto == 17u && nat ? 6u : c.proto == 1u && !nat ? 2u : NONE;
+        if (x != NONE) {
+            if (c.tl < need) c.verdict |= V_MALFORMED;
+            else { c.l4_needed = true; c.xoff = x; }
+        }
+    }
+    return c;
+}
+
+// The IPv6 transport dispatch once net_len, proto (the next header reached) and tl are known
+// (pico_ipv6.c:790, pico_transport_crc_check pico_socket.c:1919-1958); b9 = byte 9 of the IPv6
+// header, room = the bytes behind net_len.  RX: the reference dispatches on byte 9 (kept in ipcrc)
+// unless nxd (F_NXD: on the next header) -- byte 9 = 17 on a TCP next header reads the UDP crc
+// field; the field read (the UDP crc: is it present?; the ICMPv6 type) must lie in the frame, and
+// the region is read ahead to it (ext).  TX: the crc field to compute, the transport at least its
+// header.  xoff is the dispatch's field (NONE: none) whether or not the lengths then fit.
+struct Ip6 {
+    uint32_t xoff, ipcrc, ext;
+    bool l4_needed, malformed;
+};
+[[maybe_unused]] __device__ __forceinline__ Ip6 ipv6_dispatch(uint32_t proto, uint32_t b9, uint32_t tl,
+                                                              uint32_t room, bool tx, bool nxd) {
+    Ip6 d{NONE, 0u, tl, false, false};
+    if (!tx) {
+        d.ipcrc = b9;
+        const bool ref17 = !nxd && b9 == 17u;
+        const uint32_t ahead = proto == 58u ? 1u : 8u;
+        if (proto == 6u && !ref17) { d.l4_needed = true; return d; }
+        if (proto != 6u && proto != 17u && proto != 58u) return d;
+        d.xoff = proto == 58u ? 0u : 6u;
+        if (room < ahead) d.malformed = true;
+        else { d.l4_needed = true; d.ext = max(tl, ahead); }
+    } else if (proto == 6u || proto == 17u || proto == 58u) {
+        d.xoff = proto == 6u ? 16u : proto == 17u ? 6u : 2u;
+        if (tl < (proto == 6u ? 20u : proto == 17u ? 8u : 4u)) d.malformed = true;
+        else d.l4_needed = true;
+    }
+    return d;
+}
+
+// pico_ipv4_nat_outbound / _inbound (modules/pico_nat.c:424-545) after the host's tuple lookup, on
+// a parsed datagram: the record's dir (1 outbound: source + source port, 2 inbound: destination +
+// destination port, else none) -> NS_SKIP / NS_BAD (a TCP / UDP transport shorter than its header)
+// / NS_XLATE | dir << 4 / NS_HDR (ICMP: only the header checksum), and for NS_XLATE the address
+// delta da: the rewritten words enter the sums as deltas (header, pseudo header, region), so the
+// one pass over the old bytes gives the checksums of the new ones (RFC 1624's incremental update,
+// applied to full sums).  The old port is fetched by the caller.
+struct NatStage {
+    uint32_t ns, da;
+};
+[[maybe_unused]] __device__ __forceinline__ NatStage nat_stage(bool parsed, uint32_t post, uint32_t proto,
+                                                               bool l4_needed, uint32_t dir, uint32_t old_addr,
+                                                               uint32_t new_addr) {
+    if (!parsed || post != 0u || (dir != 1u && dir != 2u)) return {NS_SKIP, 0u};
+    if (proto == 1u) return {NS_HDR, 0u};
+    if (proto != 6u && proto != 17u) return {NS_SKIP, 0u};
+    if (!l4_needed) return {NS_BAD, 0u};
+    return {NS_XLATE | (dir << 4),
+            (new_addr & 0xFFFFu) + (new_addr >> 16) - (old_addr & 0xFFFFu) - (old_addr >> 16)};
+}
+
+template <int MODE>
 __device__ __forceinline__ void sorted_batch(const FlatArgs& p, SortedWaveLds& L, uint4* stage, uint32_t lane,
                                              uint64_t f0) {
     constexpr bool IPV4 = MODE == 1, IPV6 = MODE == 2, ETH = MODE == 3;
@@ -417,8 +561,7 @@ __device__ __forceinline__ void sorted_batch(const FlatArgs& p, SortedWaveLds& L
                     if (!inside && i < nlh) hw[i] = load_chunk(a0, i);
             }
         }
-        // MODE 3: the Ethernet header first (pico_ethernet_receive / pico_eth_receive,
-        // pico_ethernet.c:180-235), then the IP header at +14 (the region moves there).
+        // MODE 3: the Ethernet header first, then the IP header at +14 (the region moves there).
         uint32_t fam = IPV6 ? 6u : 4u, pos = r, avail = len;
         if constexpr (ETH) {
             fam = 0;
@@ -426,16 +569,8 @@ __device__ __forceinline__ void sorted_batch(const FlatArgs& p, SortedWaveLds& L
                 uint32_t M[2], T[1];
                 window_words<2, true>(hw, r, M);
                 window_words<1, true>(hw, r + 12u, T);
-                const uint32_t m0 = M[0], m1 = M[1] & 0xFFFFu, et = T[0] & 0xFFFFu;   // ethertype, LE word
-                const bool mine = !(p.flags & F_MACF) || tx || (m0 == p.mac_lo && m1 == p.mac_hi) ||
-                                  (m0 & 0xFFFFFFu) == 0x5E0001u || (m0 & 0xFFFFu) == 0x3333u ||
-                                  (m0 == 0xFFFFFFFFu && m1 == 0xFFFFu);
-                if (!mine) l2v = V_DROP_L2;
-                else if (et == 0x0608u) l2v = V_ARP;          // 0x0806 -> pico_arp_receive
-                else if (et == 0x0008u) fam = 4u;             // 0x0800
-                else if (et == 0xDD86u) fam = 6u;             // 0x86DD
-                else l2v = V_DROP_L2;
-                if (fam) {
+                EthClass c = eth_classify(M[0], M[1], T[0], p.flags, tx, p.mac_lo, p.mac_hi);
+                if (c.fam) {
                     pos = r + 14u;
                     off += 14u;
                     avail = len - 14u;
@@ -445,106 +580,51 @@ __device__ __forceinline__ void sorted_batch(const FlatArgs& p, SortedWaveLds& L
                     odd = r & 1u;
                     uint32_t V[1];
                     window_words<1, true>(hw, pos, V);
-                    // IS_IPV4 / IS_IPV6 (pico_ethernet.c:145,164); no byte to read: MALFORMED
-                    if (avail == 0u) fam = 0;
-                    else if ((V[0] & 0xF0u) != (fam << 4)) { fam = 0; l2v = V_DROP_L2; }
+                    c = eth_version(c, avail, V[0]);
                 }
+                l2v = c.l2v;
+                fam = c.fam;
             }
         }
         if (IPV4 || (ETH && fam == 4u)) {
+            const bool nat = IPV4 && (p.flags & F_NAT);
+            if (nat) l2v = NS_SKIP;
             if (avail >= 20) {
                 uint32_t H[5];
                 window_words<5, ETH>(hw, pos, H);
-                const uint32_t ihl = H[0] & 0x0Fu;
-                hl = 20u + (ihl > 5u ? 4u * (ihl - 5u) : 0u);
-                const uint32_t tot = (((H[0] >> 16) & 0xFFu) << 8) | (H[0] >> 24);
-                proto = (H[2] >> 8) & 0xFFu;
-                ipcrc = H[2] >> 16;
-                tl = (tot - hl) & 0xFFFFu;                              // uint16 wrap, pico_ipv4.c:395
-                const uint32_t max_allowed = (avail - 20u) & 0xFFFFu;   // pico_ipv4.c:386
-                if (!(hl > avail || (!tx && tl > max_allowed) || hl + tl > avail)) {
-                    parsed = true;
-                    verdict = 0;
-                    span = ext = hl + tl;
-#pragma unroll
-                    for (int m = 0; m < 5; ++m) hdr20 = dot2_add(H[m], hdr20);
-                    pseudo = (H[3] & 0xFFFFu) + (H[3] >> 16) + (H[4] & 0xFFFFu) + (H[4] >> 16) +
-                             (proto << 8) + (((tl & 0xFFu) << 8) | (tl >> 8));
+                const Ip4 c = ipv4_classify(H, avail, tx, nat);
+                verdict = c.verdict, hl = c.hl, tl = c.tl, proto = c.proto, ipcrc = c.ipcrc;
+                pseudo = c.pseudo, hdr20 = c.hdr20, post = c.post, parsed = c.parsed, l4_needed = c.l4_needed;
+                if (parsed) {
+                    span = ext = post ? hl : hl + tl;
                     if (hl > 20u) optend = r + hl;
-                    // after the header check (sorted_finish): pico_ipv4_is_valid_src (:425-428,
-                    // :187-229 -- 255.255.255.255, 224-254.x.x.x, 127/8 from a device that is not
-                    // "loop"), the evil bit (:431-435), IHL < 5 (:438-443): discarded; MF or an
-                    // offset (:446-455): handed to reassembly.  Then only the header is summed.
-                    const uint32_t frag = ((H[1] >> 8) & 0xFF00u) | (H[1] >> 24);
-                    const uint32_t s0 = H[3] & 0xFFu;
-                    const bool bad_src = H[3] == 0xFFFFFFFFu || (s0 != 0xFFu && (s0 & 0xE0u) == 0xE0u) || s0 == 0x7Fu;
-                    if (!tx && (bad_src || (frag & 0x8000u) || ihl < 5u)) post = PV_DROP;
-                    else if (frag & 0x3FFFu) post = PV_FRAG;
-                    if (post) {
-                        span = ext = hl;
-                    } else if (!tx) {
-                        if (proto == 6u) {
-                            l4_needed = true;
-                        } else if (proto == 17u) {     // the UDP crc field lies past the frame: MALFORMED
-                            if (hl + 8u > avail) { post = PV_DROP; span = ext = hl; }
-                            else { l4_needed = true; xpos = r + hl + 6u; ext = max(span, hl + 8u); }
-                        }
-                    } else {
-                        // NAT (F_NAT): TCP and UDP are recomputed in full (pico_nat.c:443-449,
-                        // :461-465, :511-517, :527-532), ICMP only gets its header checksum
-                        const bool nat = IPV4 && (p.flags & F_NAT);
-                        if (proto == 6u) {
-                            if (tl < 20u) verdict |= V_MALFORMED;
-                            else { l4_needed = true; xpos = r + hl + 16u; }
-                        } else if (proto == 17u && nat) {
-                            if (tl < 8u) verdict |= V_MALFORMED;
-                            else { l4_needed = true; xpos = r + hl + 6u; }
-                        } else if (proto == 1u && !nat) {
-                            if (tl < 8u) verdict |= V_MALFORMED;
-                            else { l4_needed = true; xpos = r + hl + 2u; }
-                        }
-                    }
+                    if (c.xoff != NONE) xpos = r + hl + c.xoff;
+                    if (!tx && c.xoff != NONE) ext = max(span, hl + 8u);   // RX UDP: the crc field is read
                 }
-            }
-            if constexpr (IPV4) {
-                // pico_ipv4_nat_outbound / _inbound (modules/pico_nat.c:424-545) after the host's
-                // tuple lookup: record {addr, port, dir} per frame (dir 1 outbound: src + sport,
-                // 2 inbound: dst + dport, 0 none).  The rewritten words enter the sums as deltas
-                // (header, pseudo header, region), so the one pass over the old bytes gives the
-                // checksums of the new ones (RFC 1624's incremental update, applied to full sums).
-                if (p.flags & F_NAT) {
-                    const uint8_t* nat = reinterpret_cast<const uint8_t*>(((uint64_t)p.mac_hi << 32) | p.mac_lo);
+                if (nat) {
+                    // the frame's record {addr, port | dir << 16}
+                    const uint8_t* rec = reinterpret_cast<const uint8_t*>(((uint64_t)p.mac_hi << 32) | p.mac_lo);
                     uint2 rw = make_uint2(0u, 0u);
-                    if (lane < cnt) rw = *reinterpret_cast<const uint2*>(nat + 8ull * (f0 + lane));
+                    if (lane < cnt) rw = *reinterpret_cast<const uint2*>(rec + 8ull * (f0 + lane));
                     const uint32_t dir = (rw.y >> 16) & 0xFFu;
-                    l2v = NS_SKIP;
-                    if (parsed && post == 0u && (dir == 1u || dir == 2u)) {
-                        if ((proto == 6u || proto == 17u) && !l4_needed) {
-                            l2v = NS_BAD;                            // transport shorter than its header
-                        } else if (proto == 6u || proto == 17u) {
-                            uint32_t H[5];
-                            window_words<5, false>(hw, r, H);
-                            const uint32_t old = dir == 1u ? H[3] : H[4];
-                            const uint32_t da = (rw.x & 0xFFFFu) + (rw.x >> 16) - (old & 0xFFFFu) - (old >> 16);
-                            // the old port: from the LDS stage, or -- a frame outside the wave's window
-                            // (staged false: outside the wave's <= 2 GiB window around its first frame) -- from memory
-                            const uint32_t pb = r + hl + (dir == 1u ? 0u : 2u);
-                            uint32_t op;
-                            if (staged) {
-                                const uint8_t* row = reinterpret_cast<const uint8_t*>(stage + lane * HW);
-                                const uint32_t sw = (lane & (HW - 1)) << 4;
-                                op = (uint32_t)row[pb ^ sw] | ((uint32_t)row[(pb + 1u) ^ sw] << 8);
-                            } else {
-                                const uint8_t* q = fp + (pb - r);
-                                op = (uint32_t)q[0] | ((uint32_t)q[1] << 8);
-                            }
-                            hdr20 += da;
-                            pseudo += da;
-                            p_all = da + (rw.y & 0xFFFFu) - op;     // the region's share of both words
-                            l2v = NS_XLATE | (dir << 4);
-                        } else if (proto == 1u) {
-                            l2v = NS_HDR;
+                    const NatStage s = nat_stage(parsed, post, proto, l4_needed, dir, dir == 1u ? H[3] : H[4], rw.x);
+                    l2v = s.ns;
+                    if ((s.ns & 15u) == NS_XLATE) {
+                        // the old port: from the LDS stage, or -- a frame outside the wave's window
+                        // (staged false: outside the wave's <= 2 GiB window around its first frame) -- from memory
+                        const uint32_t pb = r + hl + (dir == 1u ? 0u : 2u);
+                        uint32_t op;
+                        if (staged) {
+                            const uint8_t* row = reinterpret_cast<const uint8_t*>(stage + lane * HW);
+                            const uint32_t sw = (lane & (HW - 1)) << 4;
+                            op = (uint32_t)row[pb ^ sw] | ((uint32_t)row[(pb + 1u) ^ sw] << 8);
+                        } else {
+                            const uint8_t* q = fp + (pb - r);
+                            op = (uint32_t)q[0] | ((uint32_t)q[1] << 8);
                         }
+                        hdr20 += s.da;
+                        pseudo += s.da;
+                        p_all = s.da + (rw.y & 0xFFFFu) - op;     // the region's share of both words
                     }
                 }
             }
@@ -570,48 +650,30 @@ __device__ __forceinline__ void sorted_batch(const FlatArgs& p, SortedWaveLds& L
                         proto = w >> 24;
                     }
                 }
-                tl = (plen - (net_len - 40u)) & 0xFFFFu;                // pico_ipv6.c:790
+                tl = (plen - (net_len - 40u)) & 0xFFFFu;
                 if (post == PV_FRAG) {
                     parsed = true;                   // handed to reassembly: nothing to sum
                     verdict = 0;
                 } else if (walked && net_len >= 40u && net_len <= avail && net_len + tl <= avail) {
-                    uint32_t addr = 0, xrel = NONE;
+                    uint32_t addr = 0;
 #pragma unroll
                     for (int m = 2; m < 10; ++m) addr = dot2_add(H[m], addr);
                     pseudo = addr + (((tl & 0xFFu) << 8) | (tl >> 8)) + (proto << 8);
-                    parsed = true;
-                    verdict = 0;
-                    ext = tl;
-                    if (!tx) {
-                        // pico_transport_crc_check's proto is byte 9 (kept in ipcrc) unless F_NXD
-                        ipcrc = (H[2] >> 8) & 0xFFu;
-                        const bool ref17 = !(p.flags & F_NXD) && ipcrc == 17u;
-                        if (proto == 6u && !ref17) {
-                            l4_needed = true;
-                        } else if (proto == 17u || proto == 6u) {   // the UDP crc field is read
-                            if (net_len + 8u > avail) { parsed = false; verdict = V_MALFORMED; }
-                            else { l4_needed = true; xrel = 6u; ext = max(tl, 8u); }
-                        } else if (proto == 58u) {
-                            if (net_len + 1u > avail) { parsed = false; verdict = V_MALFORMED; }
-                            else { l4_needed = true; xrel = 0u; ext = max(tl, 1u); }
-                        }
-                    } else {
-                        const uint32_t need = proto == 6u ? 20u : proto == 17u ? 8u : 4u;
-                        if (proto == 6u || proto == 17u || proto == 58u) {
-                            if (tl < need) { parsed = false; verdict = V_MALFORMED; }
-                            else { l4_needed = true; xrel = proto == 6u ? 16u : proto == 17u ? 6u : 2u; }
-                        }
-                    }
-                    if (parsed) {
+                    const Ip6 d = ipv6_dispatch(proto, (H[2] >> 8) & 0xFFu, tl, avail - net_len, tx,
+                                                (p.flags & F_NXD) != 0u);
+                    ipcrc = d.ipcrc;
+                    if (!d.malformed) {
+                        parsed = true;
+                        verdict = 0;
+                        l4_needed = d.l4_needed;
+                        ext = d.ext;
                         off += net_len;
                         fp = p.base + off;
                         r = (uint32_t)(reinterpret_cast<uintptr_t>(fp) & 15u);
                         a0off = off - r;
                         odd = r & 1u;
                         span = tl;
-                        if (xrel != NONE) xpos = r + xrel;
-                    } else {
-                        ext = 0;
+                        if (d.xoff != NONE) xpos = r + d.xoff;
                     }
                 }
             }
@@ -748,11 +810,11 @@ __device__ __forceinline__ void sorted_batch(const FlatArgs& p, SortedWaveLds& L
     RawArgs ra{p.base, p.base_len, nullptr, 0, 0, 0, 0, -1, 0u, 0u, nullptr, nullptr};
     if (m) {
         if (any_odd) {
-            if (any_xo) sorted_rounds<CPL, true, NT, true, SMALL>(ra, L, e, m);
-            else sorted_rounds<CPL, true, NT, false, SMALL>(ra, L, e, m);
+            if (any_xo) sorted_rounds<true, true>(ra, L, e, m);
+            else sorted_rounds<true, false>(ra, L, e, m);
         } else {
-            if (any_xo) sorted_rounds<CPL, false, NT, true, SMALL>(ra, L, e, m);
-            else sorted_rounds<CPL, false, NT, false, SMALL>(ra, L, e, m);
+            if (any_xo) sorted_rounds<false, true>(ra, L, e, m);
+            else sorted_rounds<false, false>(ra, L, e, m);
         }
     }
     __builtin_amdgcn_wave_barrier();
@@ -848,28 +910,8 @@ __device__ __forceinline__ uint32_t pairing(uint32_t v, bool odd) {
 // COMPACT stream over the frames' own lines in frame order for slot rings and scattered frames, its
 // chunk -> line map a binary search per chunk.)
 
-// Returns false (nothing written) for a wave whose frames are not streamed: they are not back to
-// back, or after the loop, the wave holds a frame the stream does not finish (below).  NATM: the NAT batch (F_NAT), its own instantiation so the RX / TX waves
-// carry none of its registers or instructions.  V6: the IPv6 batch (MODE 2) for datagrams whose
-// transport follows the 40-byte header (descriptor seed 0; RX next header TCP / UDP / ICMPv6 --
-// anything else needs the extension-header walk: the sorted rounds).  ETH: the Ethernet batch
-// (MODE 3): IPv4 and IPv6 behind the 14-byte header (ARP / dropped frames need no sums; a wave
-// holding an IPv6 datagram that needs the extension-header walk falls back after the loop).
-// (eth6_field, uniform64, lds_pair: used by the fused modes' stream waves only -- the RAW-mode
+// (The header-rule helpers, uniform64, lds_pair: used by the fused modes only -- the RAW-mode
 // translation unit, SORTED_MODE 0, instantiates none of them.)
-// MODE 3 stream, an IPv6 frame: where the transport field the finish reads lies (relative to the
-// transport start; NONE = none) -- RX: the UDP crc (present?) when byte 9 (the reference's dispatch,
-// or with F_NXD the next header) says UDP, the ICMPv6 type; TX: the crc field to compute
-// (sorted_batch's MODE 2 rules)
-[[maybe_unused]] __device__ __forceinline__ uint32_t eth6_field(bool tx, uint32_t nh, uint32_t b9, bool nxd) {
-    if (!tx) {
-        const bool ref17 = !nxd && b9 == 17u;
-        if (nh == 6u && !ref17) return NONE;
-        if (nh == 17u || nh == 6u) return 6u;
-        return nh == 58u ? 0u : NONE;
-    }
-    return nh == 6u ? 16u : nh == 17u ? 6u : nh == 58u ? 2u : NONE;
-}
 
 // The even-domain sum of the head window's bytes [a, b) (window positions, b <= 16 * N): the
 // window starts on a 16-byte line of the span, so a byte's parity in the window is its parity there.
@@ -933,8 +975,7 @@ __device__ __forceinline__ bool stream_finish(const FlatArgs& p, StreamLds& S, u
     // the frame's offset again, from the span (a 64-bit value less to keep across the loop)
     const uint64_t off = valid ? lo + rel - reinterpret_cast<uintptr_t>(p.base) : 0u;
     if constexpr (V6) {
-        // pico_ipv6_process_in / pico_transport_crc_check as sorted_batch's MODE 2 (seed 0, no
-        // extension header): lengths, byte-9 dispatch (ipcrc), the field, the pseudo header
+        // MODE 2 with seed 0 and no extension header: lengths, the pseudo header, the dispatch
         uint32_t verdict = V_MALFORMED, tl = 0, proto = 0, ipcrc = 0, pseudo = 0, xo = NONE;
         bool parsed = false, l4_needed = false, walk = false;
         if (valid) {
@@ -949,23 +990,13 @@ __device__ __forceinline__ bool stream_finish(const FlatArgs& p, StreamLds& S, u
 #pragma unroll
                 for (int m = 2; m < 10; ++m) addr = dot2_add(H[m], addr);
                 pseudo = addr + (((tl & 0xFFu) << 8) | (tl >> 8)) + (proto << 8);
-                parsed = true;
-                verdict = 0;
-                if (!tx) {
-                    ipcrc = (H[2] >> 8) & 0xFFu;
-                    const bool ref17 = !(p.flags & F_NXD) && ipcrc == 17u;
-                    if (proto == 6u && !ref17) {
-                        l4_needed = true;
-                    } else if (proto == 17u || proto == 6u) {
-                        if (48u > len) { parsed = false; verdict = V_MALFORMED; }
-                        else { l4_needed = true; xo = 6u; }
-                    } else if (proto == 58u) {
-                        if (41u > len) { parsed = false; verdict = V_MALFORMED; }
-                        else { l4_needed = true; xo = 0u; }
-                    }
-                } else if (proto == 6u || proto == 17u || proto == 58u) {
-                    if (tl < (proto == 6u ? 20u : proto == 17u ? 8u : 4u)) { parsed = false; verdict = V_MALFORMED; }
-                    else { l4_needed = true; xo = proto == 6u ? 16u : proto == 17u ? 6u : 2u; }
+                const Ip6 d = ipv6_dispatch(proto, (H[2] >> 8) & 0xFFu, tl, len - 40u, tx, (p.flags & F_NXD) != 0u);
+                ipcrc = d.ipcrc;
+                if (!d.malformed) {
+                    parsed = true;
+                    verdict = 0;
+                    l4_needed = d.l4_needed;
+                    xo = d.xoff;
                 }
             }
         }
@@ -996,43 +1027,28 @@ __device__ __forceinline__ bool stream_finish(const FlatArgs& p, StreamLds& S, u
         STAMP(3);
         return true;
     }
-    // the header (pico_ipv4_process_in's checks and dispatch, as sorted_batch)
     uint32_t verdict = V_MALFORMED, hl = 0, tl = 0, proto = 0, ipcrc = 0, pseudo = 0, hdr20 = 0, post = 0;
     uint32_t l2v = natm ? NS_SKIP : 0u, nop = 0, nnw = 0;   // NAT: state, old / new port (frame pairing)
-    bool parsed = false, l4_needed = false, hasx = false, nat_opt = false, ip4 = valid, eth6 = false;
+    uint32_t xo4 = NONE;                                    // the IPv4 transport's field (NONE: none)
+    bool parsed = false, l4_needed = false, nat_opt = false, ip4 = valid, eth6 = false;
     bool walk6 = false;
     const uint32_t ilen = len - L2;
-    // MODE 3 IPv6 frames (as sorted_batch's MODE 3 -> MODE 2 path, seed 0, no extension header):
-    // transport sum, field, pseudo header from the prefixes
+    // MODE 3 IPv6 frames (seed 0, no extension header): transport sum, field, pseudo header from
+    // the prefixes
     uint32_t v6sum = 0u, v6x = 0u;
     if constexpr (ETH) {
-        // pico_ethernet_receive (pico_ethernet.c:180-235): destination filter, ethertype, version
         ip4 = false;
         if (valid) {
-            uint32_t M[2], T[1];
+            uint32_t M[2], T[1], V[1];
             lds_words<2>(wl, r, M);
             lds_words<1>(wl, r + 12u, T);
-            const uint32_t m0 = M[0], m1 = M[1] & 0xFFFFu, et = T[0] & 0xFFFFu;
-            const bool mine = !(p.flags & F_MACF) || tx || (m0 == p.mac_lo && m1 == p.mac_hi) ||
-                              (m0 & 0xFFFFFFu) == 0x5E0001u || (m0 & 0xFFFFu) == 0x3333u ||
-                              (m0 == 0xFFFFFFFFu && m1 == 0xFFFFu);
-            if (!mine) l2v = V_DROP_L2;
-            else if (et == 0x0608u) l2v = V_ARP;
-            else if (et == 0xDD86u) {                    // IPv6 (pico_ethernet.c:162-176)
-                if (ilen != 0u) {
-                    uint32_t V[1];
-                    lds_words<1>(wl, r + 14u, V);
-                    if ((V[0] & 0xF0u) != 0x60u) l2v = V_DROP_L2;
-                    else eth6 = true;
-                }
-            }
-            else if (et != 0x0008u) l2v = V_DROP_L2;
-            else if (ilen != 0u) {
-                uint32_t V[1];
-                lds_words<1>(wl, r + 14u, V);
-                if ((V[0] & 0xF0u) != 0x40u) l2v = V_DROP_L2;
-                else ip4 = true;
-            }
+            // the first IP byte, read whatever the ethertype: in the lane's LDS row (r + 14 <= 29),
+            // and eth_version ignores it where the frame has none (it then is the next frame's)
+            lds_words<1>(wl, r + 14u, V);
+            const EthClass c = eth_version(eth_classify(M[0], M[1], T[0], p.flags, tx, p.mac_lo, p.mac_hi), ilen, V[0]);
+            l2v = c.l2v;
+            ip4 = c.fam == 4u;
+            eth6 = c.fam == 6u;
         }
     }
     walk6 = eth6 && seeded;
@@ -1041,25 +1057,19 @@ __device__ __forceinline__ bool stream_finish(const FlatArgs& p, StreamLds& S, u
         lds_words<3>(wl, r + 14u, H);
         tl = ((H[1] & 0xFFu) << 8) | ((H[1] >> 8) & 0xFFu);
         proto = (H[1] >> 16) & 0xFFu;
-        const uint32_t b9 = (H[2] >> 8) & 0xFFu;
         if (!tx && proto != 6u && proto != 17u && proto != 58u) {
             walk6 = true;                                // extension headers: the sorted rounds
         } else if (40u + tl <= ilen) {
             const bool odd6 = r & 1u;
             pseudo = pairing(P1 - P0, odd6) + (((tl & 0xFFu) << 8) | (tl >> 8)) + (proto << 8);
-            parsed = true;
-            verdict = 0;
-            const uint32_t xo = eth6_field(tx, proto, b9, (p.flags & F_NXD) != 0u);
-            if (!tx) {
-                ipcrc = b9;
-                if (xo == 6u && 48u > ilen) { parsed = false; verdict = V_MALFORMED; }
-                else if (xo == 0u && 41u > ilen) { parsed = false; verdict = V_MALFORMED; }
-                else l4_needed = proto == 6u || proto == 17u || proto == 58u;
-            } else if (xo != NONE) {
-                if (tl < (proto == 6u ? 20u : proto == 17u ? 8u : 4u)) { parsed = false; verdict = V_MALFORMED; }
-                else l4_needed = true;
+            const Ip6 d = ipv6_dispatch(proto, (H[2] >> 8) & 0xFFu, tl, ilen - 40u, tx, (p.flags & F_NXD) != 0u);
+            ipcrc = d.ipcrc;
+            if (!d.malformed) {
+                parsed = true;
+                verdict = 0;
+                l4_needed = d.l4_needed;
             }
-            if (xo != NONE) {
+            if (d.xoff != NONE) {
                 const uint32_t xe6 = P4 - P3;
                 v6x = odd6 ? ((xe6 >> 8) | (xe6 << 8)) & 0xFFFFu : xe6;
                 v6sum = tx ? pairing(P2 - P1 - xe6, odd6) + v6x : pairing(P2 - P1, odd6);
@@ -1071,70 +1081,28 @@ __device__ __forceinline__ bool stream_finish(const FlatArgs& p, StreamLds& S, u
     if (ETH ? ip4 && ilen >= 20u : valid) {
         uint32_t H[5];
         lds_words<5>(wl, r + L2, H);
-        const uint32_t ihl = H[0] & 0x0Fu;
-        hl = 20u + (ihl > 5u ? 4u * (ihl - 5u) : 0u);
-        const uint32_t tot = (((H[0] >> 16) & 0xFFu) << 8) | (H[0] >> 24);
-        proto = (H[2] >> 8) & 0xFFu;
-        ipcrc = H[2] >> 16;
-        tl = (tot - hl) & 0xFFFFu;
-        const uint32_t max_allowed = (ilen - 20u) & 0xFFFFu;
-        if (!(hl > ilen || (!tx && tl > max_allowed) || hl + tl > ilen)) {
-            parsed = true;
-            verdict = 0;
-#pragma unroll
-            for (int m = 0; m < 5; ++m) hdr20 = dot2_add(H[m], hdr20);
-            pseudo = (H[3] & 0xFFFFu) + (H[3] >> 16) + (H[4] & 0xFFFFu) + (H[4] >> 16) + (proto << 8) +
-                     (((tl & 0xFFu) << 8) | (tl >> 8));
-            const uint32_t frag = ((H[1] >> 8) & 0xFF00u) | (H[1] >> 24);
-            const uint32_t s0 = H[3] & 0xFFu;
-            const bool bad_src = H[3] == 0xFFFFFFFFu || (s0 != 0xFFu && (s0 & 0xE0u) == 0xE0u) || s0 == 0x7Fu;
-            if (!tx && (bad_src || (frag & 0x8000u) || ihl < 5u)) post = PV_DROP;
-            else if (frag & 0x3FFFu) post = PV_FRAG;
-            if (!post && !tx) {
-                if (proto == 6u) {
-                    l4_needed = true;
-                } else if (proto == 17u) {
-                    if (hl + 8u > ilen) post = PV_DROP;
-                    else { l4_needed = true; hasx = true; }
-                }
-            } else if (!post) {
-                // NAT: TCP and UDP recomputed in full, ICMP only its header checksum (as sorted_batch)
-                if (proto == 6u) {
-                    if (tl < 20u) verdict |= V_MALFORMED;
-                    else { l4_needed = true; hasx = true; }
-                } else if (proto == (natm ? 17u : 1u)) {
-                    if (tl < 8u) verdict |= V_MALFORMED;
-                    else { l4_needed = true; hasx = true; }
-                }
-            }
-            // NAT (pico_nat.c:424-545): the rewritten address enters the header and pseudo sums as
-            // a delta, the port the region's (below) -- sorted_batch's NAT stage, with the old port
-            // from the head window (a datagram with options falls back to the sorted rounds)
-            if constexpr (NATM) {
-                const uint32_t dir = (rw.y >> 16) & 0xFFu;
-                l2v = NS_SKIP;
-                if (post == 0u && (dir == 1u || dir == 2u)) {
-                    if ((proto == 6u || proto == 17u) && !l4_needed) {
-                        l2v = NS_BAD;
-                    } else if (proto == 6u || proto == 17u) {
-                        const uint32_t old = dir == 1u ? H[3] : H[4];
-                        const uint32_t da = (rw.x & 0xFFFFu) + (rw.x >> 16) - (old & 0xFFFFu) - (old >> 16);
-                        hdr20 += da;
-                        pseudo += da;
-                        if (hl == 20u) nop = lds_pair(wl, r + 20u + (dir == 1u ? 0u : 2u));
-                        else nat_opt = true;
-                        nnw = rw.y & 0xFFFFu;
-                        l2v = NS_XLATE | (dir << 4);
-                    } else if (proto == 1u) {
-                        l2v = NS_HDR;
-                    }
-                }
+        const Ip4 c = ipv4_classify(H, ilen, tx, natm);
+        verdict = c.verdict, hl = c.hl, tl = c.tl, proto = c.proto, ipcrc = c.ipcrc;
+        pseudo = c.pseudo, hdr20 = c.hdr20, post = c.post, parsed = c.parsed, l4_needed = c.l4_needed;
+        xo4 = c.xoff;
+        if constexpr (NATM) {
+            // the old port from the head window (a datagram with options falls back to the sorted
+            // rounds); the port's delta enters the region's sum below
+            const uint32_t dir = (rw.y >> 16) & 0xFFu;
+            const NatStage s = nat_stage(parsed, post, proto, l4_needed, dir, dir == 1u ? H[3] : H[4], rw.x);
+            l2v = s.ns;
+            if ((s.ns & 15u) == NS_XLATE) {
+                hdr20 += s.da;
+                pseudo += s.da;
+                if (hl == 20u) nop = lds_pair(wl, r + 20u + (dir == 1u ? 0u : 2u));
+                else nat_opt = true;
+                nnw = rw.y & 0xFFFFu;
             }
         }
     }
     // MODE 1 (no parse in the loop: P1 at the options start, P2 at the frame's end): the options,
     // the field and any bytes past the datagram from the head window, else the sorted rounds
-    const uint32_t xo4 = (!tx || proto == 17u) ? 6u : proto == 6u ? 16u : 2u;
+    const bool hasx = xo4 != NONE;
     const bool v4 = parsed && !eth6;                   // an IPv4 datagram with sums to take
     const bool fx = ETH && tx && proto == 6u && hl == 20u;   // MODE 3 TX TCP crc: by prefixes (50)
     const bool tail = v4 && hl + tl < ilen;
@@ -1181,6 +1149,14 @@ __device__ __forceinline__ bool stream_finish(const FlatArgs& p, StreamLds& S, u
     return true;
 }
 
+// Returns false (nothing written) for a wave whose frames are not streamed: they are not back to
+// back, or, after the loop, the wave holds a frame the stream does not finish (stream_finish).
+// NATM: the NAT batch (F_NAT), its own instantiation so the RX / TX waves carry none of its
+// registers or instructions.  V6: the IPv6 batch (MODE 2) for datagrams whose transport follows
+// the 40-byte header (descriptor seed 0; RX next header TCP / UDP / ICMPv6 -- anything else needs
+// the extension-header walk: the sorted rounds).  ETH: the Ethernet batch (MODE 3): IPv4 and IPv6
+// behind the 14-byte header (ARP / dropped frames need no sums; a wave holding an IPv6 datagram
+// that needs the extension-header walk falls back after the loop).
 template <bool NATM, bool V6 = false, bool ETH = false>
 __device__ __forceinline__ bool stream_batch(const FlatArgs& p, StreamLds& S, uint32_t lane, uint64_t f0) {
     constexpr uint32_t L2 = ETH ? 14u : 0u;   // the IPv4 header's offset in the frame
@@ -1189,7 +1165,7 @@ __device__ __forceinline__ bool stream_batch(const FlatArgs& p, StreamLds& S, ui
     const bool tx = (p.flags & 2u) != 0;
     uint4 dcur = make_uint4(0, 0, 0, 0);
     if (lane < cnt) dcur = *reinterpret_cast<const uint4*>(p.desc + f0 + lane);
-    // NAT: the frame's record {addr, port | dir << 16} (sorted_batch's NAT stage)
+    // NAT: the frame's record {addr, port | dir << 16}
     uint2 rw = make_uint2(0u, 0u);
     if (NATM && lane < cnt)
         rw = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint8_t*>(((uint64_t)p.mac_hi << 32) | p.mac_lo) +
@@ -1295,12 +1271,7 @@ __device__ __forceinline__ bool stream_batch(const FlatArgs& p, StreamLds& S, ui
     // one step: cur is staged and summed while nxt's loads (step st + 1) are in flight
     auto step = [&](auto pf, uint32_t st, uint4 (&cur)[SCPL], uint4 (&nxt)[SCPL]) {
         const uint32_t qb = st * SQ;
-#if STREAM_LAST_NOPF
         if constexpr (decltype(pf)::value) load_step(qb + SQ, nxt);
-#else
-        (void)pf;
-        load_step(qb + SQ, nxt);
-#endif
         asm volatile("" ::: "memory");
 #pragma unroll
         for (uint32_t c = 0; c < SCPL; ++c) S.raw[sslot(64u * c + lane)] = cur[c];
@@ -1355,7 +1326,7 @@ __device__ __forceinline__ bool stream_batch(const FlatArgs& p, StreamLds& S, ui
                 if (ilen >= 40u) {
                     // (b0, b1 since the ethertype)
                     b2 = rel + 14u + min(40u + plen, ilen);
-                    const uint32_t xo = eth6_field(tx, nh, b9, (p.flags & F_NXD) != 0u);
+                    const uint32_t xo = ipv6_dispatch(nh, b9, plen, ilen - 40u, tx, (p.flags & F_NXD) != 0u).xoff;
                     if (xo != NONE && 40u + xo < ilen) {
                         x0 = rel + 54u + xo;
                         x1 = x0 + min(2u, ilen - 40u - xo);
@@ -1380,7 +1351,6 @@ __device__ __forceinline__ bool stream_batch(const FlatArgs& p, StreamLds& S, ui
         // two steps a trip, the register sets swapping roles: each step's wait covers only its own
         // loads (a copy of the next set into this one at the end of a trip would wait on them too,
         // leaving one step in flight across the wait)
-#if STREAM_LAST_NOPF
         // the last step loads nothing ahead (its next step would be past the span: 8 void loads):
         // c2v6 22.3-22.7 vs 22.9-23.5 us, c2nat 30.9-31.4 vs 31.2-31.7, c2 and c2tx the same
         // (profiles/r06/ab_stream_last_nopf.txt)
@@ -1395,13 +1365,6 @@ __device__ __forceinline__ bool stream_batch(const FlatArgs& p, StreamLds& S, ui
         } else if (st < nsteps) {
             step(std::false_type{}, st, v, vn);
         }
-#else
-        for (uint32_t st = 0; st < nsteps; st += 2) {
-            step(std::true_type{}, st, v, vn);
-            if (st + 1u >= nsteps) break;
-            step(std::true_type{}, st + 1u, vn, v);
-        }
-#endif
     } else {
         // MODE 3 (both families' parse in the loop): one step a trip, the sets copied -- the
         // two-step trip spills there
@@ -1422,9 +1385,7 @@ __device__ __forceinline__ bool stream_batch(const FlatArgs& p, StreamLds& S, ui
 
 // One wave per batch of up to 64 frames.  (A persistent grid looping over batches
 // measured slower: every wave repeats the same serial descriptor -> rounds chain.)
-// The product shape (measured): 8 chunks per lane per round, the 1-lane class for
-// frames of <= 8 chunks, non-temporal loads in the >= 16-lane rounds; 4 waves per SIMD.
-template <int MODE, bool NT = true, int CPL = 8, bool SMALL = true>
+template <int MODE>
 __global__ __launch_bounds__(64 * WPB, 16 / WPB) void csum_sorted_kernel(FlatArgs p) {
     __shared__ SortedWaveSmem<MODE != 0> lds_all[WPB];
     const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
@@ -1439,7 +1400,7 @@ __global__ __launch_bounds__(64 * WPB, 16 / WPB) void csum_sorted_kernel(FlatArg
             else done = (p.flags & F_NAT) ? stream_batch<true>(p, S.st, lane, f0) : stream_batch<false>(p, S.st, lane, f0);
             if (done) return;
         }
-        if (f0 < p.n) sorted_batch<MODE, NT, CPL, SMALL>(p, S.s, S.stage, lane, f0);
+        if (f0 < p.n) sorted_batch<MODE>(p, S.s, S.stage, lane, f0);
     }
     STAMP(3);
 }
