@@ -52,7 +52,8 @@ extern "C" {
  *   3: F_NXTHDR_DISPATCH moved to 0x8 (bit 0x4 -- ABI 1's F_REF_DISPATCH, the opposite meaning --
  *      is rejected with -EINVAL); the forwarding batch takes the host's link addresses and a
  *      carried state (pico_ipv4_pre_forward_checks in full);
- *   4: pico_csum_release_thread_scratch; the reassembly's flat-grid scratch is freed at thread exit. */
+ *   4: pico_csum_release_thread_scratch; the reassembly's flat-grid scratch is freed at thread exit;
+ *   4 (added, no bump): pico_ipv4_fragment_batch_dev -- a new entry point breaks no caller. */
 #define PICO_CSUM_ABI_VERSION 4
 
 /* picoTCP pico_err values used here (include/pico_protocol.h:27,31,38 + ENODEV) */
@@ -99,7 +100,8 @@ struct pico_csum_desc {
  *   Ethernet:              the RX / TX list, DROP_L2, ARP, | IPV6
  *   forwarding:            ACCEPT, MALFORMED, EXPIRED, LOCAL_SRC, DUPLICATE
  *   NAT:                   ACCEPT, MALFORMED, FRAG, UNTOUCHED
- *   reassembly:            ACCEPT, L4_BAD, MALFORMED */
+ *   reassembly:            ACCEPT, L4_BAD, MALFORMED
+ *   fragmentation (TX):    ACCEPT, MALFORMED */
 #define PICO_CSUM_V_ACCEPT    1u  /* delivered to the transport and every checksum the reference
                                      checks passes: hand the frame on (a stack built with CRC=0
                                      need not check it again) */
@@ -362,9 +364,60 @@ int pico_ipv6_reassemble_batch_dev(const void *d_base, uint64_t base_len, const 
                                    uint64_t out_len, const struct pico_csum_desc *d_out_desc, uint32_t *d_out_len,
                                    uint16_t *d_out_transport, uint8_t *d_verdict, uint32_t flags, void *stream);
 
+/* IPv4 TX fragmentation: the inverse of pico_ipv4_reassemble_batch_dev, fused with every
+ * fragment's header checksum and the transport checksum of the whole datagram (the batch form of
+ * pico_socket_xmit_fragments, stack/pico_socket.c:1131-1251, with pico_ipv4_frame_push's len / id /
+ * frag / pico_ipv4_checksum per frame, modules/pico_ipv4.c:1039-1079; pico_ipv4_rebound_large,
+ * :1464-1510, splits a large ICMP reply by the same rule).  One pass reads each transport byte
+ * once, writes it into its fragment and sums it; the reference copies it (memcpy) and sends
+ * fragmented UDP with crc = 0 because nothing sums the whole payload (modules/pico_udp.c:119-123).
+ *   d_dgram[]  one unfragmented datagram each: desc.off -> a 20-byte IPv4 header (IHL 5), desc.len =
+ *              20 + transport bytes (<= 65535), desc.seed = 0 -- what the reassembly batch writes.
+ *              vhl, tos, id, ttl, proto, src and dst are taken from the header; its len, frag and
+ *              crc fields are not read (the socket and IP layers set them, :1040, :1069, :1079).
+ *   split      per = (mtu - 20) & ~7 payload bytes a fragment (mtu >= 28, else -EINVAL): the
+ *              reference's rule wherever it places data correctly (mtu - 20 a multiple of 8, e.g.
+ *              1500; its frag = (written + 8) >> 3 misplaces data for any other MTU, e.g. the 1280
+ *              it uses before a socket has a device -- the evident intent there).  A datagram of
+ *              desc.len <= mtu goes out whole, count 1, frag = 0x4000 (DF, :1059); else count =
+ *              ceil((len - 20) / per), fragment k carries transport bytes [k per, min((k + 1) per,
+ *              len - 20)) behind the input's 20 header bytes with len = 20 + payload, frag =
+ *              (k per) >> 3 | 0x2000 on every fragment but the last (DF never), crc =
+ *              pico_ipv4_checksum.
+ *   d_out_desc[] per datagram: output region in d_out (off any alignment, len = capacity).  Fragment
+ *              k starts at off + k frag_stride; frag_stride a multiple of 4, >= 20 + per (else
+ *              -EINVAL).  off = 12 mod 16 with a stride that is a multiple of 16 puts every payload
+ *              on a 16-byte line (whole-line stores; the reassembly's rule).
+ *   d_groups[] 2 uint32 per datagram, the reassembly's layout, read-only: first slot in d_out_frag,
+ *              slots reserved.  d_out_frag[first + k] = {fragment k's offset in d_out, 20 + payload,
+ *              0}; reserved slots past count = {0, 0, 0}.  A group that reserves exactly count slots
+ *              lets d_out, d_out_frag and d_groups go to pico_ipv4_reassemble_batch_dev as they are.
+ *   d_out_count[g]     fragments emitted (0 when MALFORMED)
+ *   d_out_transport[g] the whole datagram's transport checksum, its crc field read as zero when it
+ *              lies inside the transport, by the TX rule of the fused batches: TCP and UDP with the
+ *              pseudo header of the template, ICMPv4 without one, 0 for other protocols; UDP is
+ *              computed and stored as it is, as the NAT batch does (pico_nat.c:464-465).  With
+ *              PICO_CSUM_F_WRITE it is stored into that crc field (in the fragment that holds it:
+ *              the first unless per < 24); without, the transport is copied verbatim -- the
+ *              reference's bytes, UDP's crc = 0 included.  Other flags: -EINVAL.
+ *   d_verdict[g]       ACCEPT, or MALFORMED = no byte of the region is written: a datagram past
+ *              base_len, len < 20 or > 65535, IHL != 5, fewer reserved slots than count, slots past
+ *              n_frag (then no slot is written either), an output region too small for
+ *              (count - 1) frag_stride + the last fragment or past out_len.  Its count is 0 and its
+ *              slots are {0, 0, 0}.
+ * No byte outside [d_out_desc[g].off, + len) is written, and inside it only the fragments' own
+ * bytes (gaps between fragments keep their contents).  Reads follow the whole-16-byte-block rule
+ * above.  d_out_frag, d_out_count, d_out_transport and d_verdict may each be NULL.  Regions and slot
+ * ranges of different datagrams must not overlap.  One workgroup per datagram, one launch. */
+int pico_ipv4_fragment_batch_dev(const void *d_base, uint64_t base_len, const struct pico_csum_desc *d_dgram,
+                                 uint32_t n_dgram, uint32_t mtu, const uint32_t *d_groups, uint32_t n_frag, void *d_out,
+                                 uint64_t out_len, const struct pico_csum_desc *d_out_desc, uint32_t frag_stride,
+                                 struct pico_csum_desc *d_out_frag, uint32_t *d_out_count, uint16_t *d_out_transport,
+                                 uint8_t *d_verdict, uint32_t flags, void *stream);
+
 /* ---------------------------------------------------------------- layer 3 */
 
-struct pico_csum_ctx;   /* device, three streams and staging slots (the uniform ring alternates two;
+struct pico_csum_ctx;  /* device, three streams and staging slots (the uniform ring alternates two;
                          * staged descriptor batches rotate over three, the third staging buffer
                          * allocated on their first call) */
 

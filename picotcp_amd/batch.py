@@ -321,6 +321,49 @@ def _reassemble(v6, base, frag_desc, n_frag, groups, out, out_desc, flags, strea
     return ol, l4, v
 
 
+def ipv4_fragment_batch(base: torch.Tensor, dgram_desc: torch.Tensor, mtu: int, groups: torch.Tensor, n_frag: int,
+                        out: torch.Tensor, out_desc: torch.Tensor, frag_stride: int, flags: int = 0,
+                        out_frag: torch.Tensor | None = None, stream=None, results=None):
+    """IPv4 TX fragmentation scatter + header checksums + the whole datagram's transport checksum
+    (pico_socket_xmit_fragments, pico_socket.c:1131-1251; pico_ipv4_frame_push, pico_ipv4.c:1039-1079):
+    the inverse of ipv4_reassemble_batch.  dgram_desc = one unfragmented datagram per descriptor
+    (20-byte header + transport), groups = uint32 (first slot, slots reserved) pairs per datagram
+    (int32 tensor of 2*n), out = uint8 device buffer; fragment k of datagram g is written at
+    out_desc[g].off + k*frag_stride, per = (mtu - 20) & ~7 payload bytes each.  out_frag (uint8
+    tensor of 16*n_frag bytes, or None) receives the fragments' descriptors.  flags: F_WRITE stores
+    the transport checksum into its crc field.  Returns (verdict uint8[n], count int32[n],
+    out_transport int16[n]); `results` may pass that triple preallocated, any of them None to skip it."""
+    for t, nm in ((base, "base"), (dgram_desc, "dgram_desc"), (groups, "groups"), (out, "out"), (out_desc, "out_desc")):
+        _require_device(t, nm)
+        if t.device != base.device:
+            raise ValueError(f"{nm} is on {t.device}, the batch on {base.device}")
+    _require_u8(base, "base")
+    _require_u8(out, "out")
+    n = groups.numel() // 2
+    if groups.element_size() != 4 or not groups.is_contiguous():
+        raise ValueError("groups must be a contiguous 32-bit tensor of (first, reserved) pairs")
+    if dgram_desc.numel() * dgram_desc.element_size() < 16 * n or out_desc.numel() * out_desc.element_size() < 16 * n:
+        raise ValueError("descriptor tensor shorter than its count")
+    dev = base.device
+    if out_frag is not None:
+        _require_device(out_frag, "out_frag")
+        if out_frag.device != dev or not out_frag.is_contiguous() or out_frag.numel() * out_frag.element_size() < 16 * n_frag:
+            raise ValueError("out_frag must be a contiguous tensor of n_frag 16-byte descriptors on the batch's device")
+    if results is None:
+        results = (torch.empty(n, dtype=torch.uint8, device=dev), torch.empty(n, dtype=torch.int32, device=dev),
+                   torch.empty(n, dtype=torch.int16, device=dev))
+    v, cnt, l4 = results
+    for t, nm, sz in ((v, "verdict", 1), (cnt, "count", 4), (l4, "out_transport", 2)):
+        if t is not None:
+            _check_out(t, n, nm, dev, sz)
+    lib = _lib.load()
+    _lib.check("pico_ipv4_fragment_batch_dev",
+               lib.pico_ipv4_fragment_batch_dev(_ptr(base), base.numel(), _ptr(dgram_desc), n, mtu, _ptr(groups), n_frag,
+                                                _ptr(out), out.numel(), _ptr(out_desc), frag_stride, _ptr(out_frag),
+                                                _ptr(cnt), _ptr(l4), _ptr(v), flags, _stream_handle(stream)))
+    return v, cnt, l4
+
+
 STREAM_OFF = 0xFF
 
 

@@ -45,6 +45,10 @@ int pico_csum_launch_reassemble(int v6, const void *base, uint64_t base_len, con
                                 uint32_t *o_len, uint16_t *o_l4, uint8_t *verdict, uint32_t flags, uint32_t flat_min,
                                 void *stream);
 int pico_csum_reasm_release_thread(void);
+int pico_csum_launch_fragment(const void *base, uint64_t base_len, const void *dgram, uint32_t n_dgram, uint32_t mtu,
+                              const uint32_t *groups, uint32_t n_frag, void *out, uint64_t out_len, const void *out_desc,
+                              uint32_t stride, void *o_frag, uint32_t *o_count, uint16_t *o_l4, uint8_t *verdict,
+                              uint32_t flags, void *stream);
 
 /* ------------------------------------------------------------------ errors */
 
@@ -591,6 +595,38 @@ int pico_ipv6_reassemble_batch_dev(const void *d_base, uint64_t base_len, const 
 {
     return reassemble_dev(1, d_base, base_len, d_frag, n_frag, d_groups, n_dgram, d_out, out_len, d_out_desc,
                           d_out_len, d_out_transport, d_verdict, flags, stream, "pico_ipv6_reassemble_batch_dev");
+}
+
+int pico_ipv4_fragment_batch_dev(const void *d_base, uint64_t base_len, const struct pico_csum_desc *d_dgram,
+                                 uint32_t n_dgram, uint32_t mtu, const uint32_t *d_groups, uint32_t n_frag, void *d_out,
+                                 uint64_t out_len, const struct pico_csum_desc *d_out_desc, uint32_t frag_stride,
+                                 struct pico_csum_desc *d_out_frag, uint32_t *d_out_count, uint16_t *d_out_transport,
+                                 uint8_t *d_verdict, uint32_t flags, void *stream)
+{
+    uint32_t per, min_stride;
+    int rc;
+    if (n_dgram == 0)
+        return 0;
+    if (!d_base || !d_dgram || !d_groups || !d_out || !d_out_desc)
+        return fail(PICO_CSUM_EINVAL, "NULL buffer");
+    if (((uintptr_t)d_dgram & 15u) != 0 || ((uintptr_t)d_out_desc & 15u) != 0 || ((uintptr_t)d_out_frag & 15u) != 0)
+        return fail(PICO_CSUM_EINVAL, "descriptor arrays must be 16-byte aligned");
+    if (((uintptr_t)d_groups & 3u) != 0 || ((uintptr_t)d_out_count & 3u) != 0 || ((uintptr_t)d_out_transport & 1u) != 0)
+        return fail(PICO_CSUM_EINVAL, "d_groups and d_out_count must be 4-byte, d_out_transport 2-byte aligned");
+    if (flags & ~PICO_CSUM_F_WRITE)
+        return fail(PICO_CSUM_EINVAL, "unknown flags 0x%x%s", flags, retired_note(flags));
+    if (mtu < 28u)
+        return fail(PICO_CSUM_EINVAL, "mtu %u: a fragment carries at least 8 payload bytes (mtu >= 28)", mtu);
+    per = (mtu - 20u) & ~7u;
+    min_stride = mtu < 20u + per ? mtu : 20u + per;
+    if (frag_stride < min_stride || (frag_stride & 3u) != 0)
+        return fail(PICO_CSUM_EINVAL, "frag_stride %u: a multiple of 4, at least %u", frag_stride, min_stride);
+    if ((rc = need_device()) != 0)
+        return rc;
+    return launch_status(pico_csum_launch_fragment(d_base, base_len, d_dgram, n_dgram, mtu, d_groups, n_frag, d_out,
+                                                   out_len, d_out_desc, frag_stride, d_out_frag, d_out_count,
+                                                   d_out_transport, d_verdict, flags, stream),
+                         "pico_ipv4_fragment_batch_dev");
 }
 
 /* ------------------------------------------------------------------ layer 3 */

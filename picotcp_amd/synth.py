@@ -433,3 +433,66 @@ def ipv6_fragments(lengths, seed: int = 23, proto: int = 6, frag_payload: int = 
         buf[int(off[j]):int(off[j]) + pieces[j].size] = pieces[j]
     flen = np.array([p.size for p in pieces], dtype=np.uint32)
     return buf, off, flen, np.array(groups, dtype=np.uint32).reshape(-1, 2)
+
+
+def fragtx_count(length: int, mtu: int) -> int:
+    """Fragments pico_ipv4_fragment_batch_dev emits for a datagram of `length` bytes (header
+    included): 1 when it fits the MTU, else ceil(transport / per), per = (mtu - 20) & ~7."""
+    per = (mtu - 20) & ~7
+    return 1 if length <= mtu else -(-(length - 20) // per)
+
+
+def ipv4_oversized(lengths, mtu: int = 1500, stride: int = 1504, seed: int = 31, proto=17, align=0, out_off: int = 12,
+                   spare: int = 0):
+    """Unfragmented IPv4 datagrams of the given TRANSPORT lengths (a 20-byte header, IHL 5, len /
+    frag / crc fields arbitrary: the fragmentation batch does not read them) for
+    pico_ipv4_fragment_batch_dev, with the arrays that place its output.  proto: one value or one
+    per datagram (6 / 17 / 1 get a plausible transport header with an arbitrary crc field);
+    align: the header's address mod 16 in the buffer, one value or one per datagram.  Output
+    regions are laid out back to back, each starting at out_off mod 16 and holding exactly the
+    fragments at `stride`; every group reserves its fragment count + `spare` slots.
+    Returns (buffer, dgram offsets uint64, dgram bytes uint32, groups uint32[n, 2] = (first slot,
+    slots reserved), out offsets uint64, out capacities uint32, n_frag, out_len)."""
+    lengths = np.asarray(lengths, dtype=np.uint32)
+    n = lengths.size
+    protos = np.broadcast_to(np.asarray(proto, dtype=np.uint8), (n,))
+    aligns = np.broadcast_to(np.asarray(align, dtype=np.uint32), (n,))
+    rng = np.random.default_rng(seed)
+    per = (mtu - 20) & ~7
+    off = np.zeros(n, np.uint64)
+    pos = 0
+    pieces = []
+    for g, L in enumerate(lengths.tolist()):
+        pr = int(protos[g])
+        h = rng.integers(0, 256, 20, dtype=np.uint8)
+        h[0], h[8], h[9] = 0x45, 64, pr
+        h[12:16] = [10, int(rng.integers(256)), int(rng.integers(256)), 1]
+        h[16:20] = [192, 168, int(rng.integers(256)), 2]
+        t = random_bytes(seed * 1000003 + g, L)
+        if pr == 6 and L >= 20:
+            t[12], t[13] = 0x50, 0x18
+        if pr == 17 and L >= 8:
+            t[4], t[5] = (L >> 8) & 0xFF, L & 0xFF
+        if pr == 1 and L >= 8:
+            t[0], t[1] = 8, 0
+        pos += (int(aligns[g]) - pos) % 16
+        off[g] = pos
+        pieces.append(np.concatenate([h, t]))
+        pos += 20 + L
+    buf = random_bytes(seed ^ 0x7F4A, pos + 16)
+    for g in range(n):
+        buf[int(off[g]):int(off[g]) + pieces[g].size] = pieces[g]
+    dlen = lengths + 20
+    cnt = np.array([fragtx_count(int(x), mtu) for x in dlen.tolist()], np.uint32)
+    reserved = cnt + np.uint32(spare)
+    first = np.concatenate([[0], np.cumsum(reserved[:-1])]).astype(np.uint32)
+    groups = np.stack([first, reserved], axis=1).astype(np.uint32)
+    last = np.where(cnt == 1, dlen, 20 + (lengths - (cnt - 1) * per)).astype(np.int64)
+    cap = ((cnt.astype(np.int64) - 1) * stride + last).astype(np.uint32)
+    ooff = np.zeros(n, np.uint64)
+    pos = 0
+    for g in range(n):
+        pos += (out_off - pos) % 16
+        ooff[g] = pos
+        pos += int(cap[g])
+    return buf, off, dlen.astype(np.uint32), groups, ooff, cap, int(reserved.sum()), pos + 16

@@ -1,0 +1,217 @@
+#!/usr/bin/env python3
+"""Measurement aid: the IPv4 TX fragmentation batch (pico_ipv4_fragment_batch_dev) beside the copy
+ceilings and beside the reassembly of the fragments it just produced -- the same payload bytes, the
+same process, the legs alternating replay by replay.
+
+Legs, per shape (datagrams of --tl transport bytes, split at --mtu into frames --stride apart):
+  fragment        ipv4_fragment_batch(F_WRITE): scatter + header checksums + the datagram's checksum
+  reassemble      ipv4_reassemble_batch on the fragments just written (the inverse gather)
+  bare_scatter_*  tools/gather_ceiling.hip's bare copy of every fragment's payload from its place in
+                  the datagram to its place in the output, nothing summed, no headers (4 waves per
+                  datagram as the fragment kernel, and flat: one wave per fragment pair)
+  seq_copy        the device's contiguous copy of the payload bytes (seq_copy, nt loads and stores)
+Each leg runs over --rotate buffer sets (the working set of one set already exceeds the 256 MiB
+Infinity Cache at the default shapes); one replay = one pass over every set, captured as a HIP
+graph; the figure is the median of --replays (>= 20) replays timed by HIP events, per call.
+Before timing, the round trip is checked at the timed size: every datagram ACCEPT on both sides
+and the TCP checksum the fragment batch stored verifying (0) in the reassembly.
+
+  python tools/fragtx_bench.py [--shape c3|9000|both] [--replays 24] [--out profiles/fragtx/x.json]
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from picotcp_amd import batch, synth  # noqa: E402
+
+HBM_PEAK = 8.0e12       # MI355X HBM3E, bytes / s (datasheet)
+
+
+def make_set(n, tl, mtu, stride, dev, seed):
+    """n TCP datagrams of tl transport bytes, 12 mod 16 into 16-byte lines, random payload."""
+    per = (mtu - 20) & ~7
+    cnt = synth.fragtx_count(20 + tl, mtu)
+    pitch = (20 + tl + 12 + 15) // 16 * 16
+    g = torch.Generator(device=dev)
+    g.manual_seed(seed)
+    buf = torch.randint(0, 256, (n * pitch + 16,), dtype=torch.uint8, device=dev, generator=g)
+    off = 12 + np.arange(n, dtype=np.int64) * pitch
+    hdr = np.zeros((n, 20), np.uint8)
+    hdr[:, 0], hdr[:, 8], hdr[:, 9] = 0x45, 64, 6
+    hdr[:, 4:6] = np.arange(n, dtype=np.uint16).byteswap().view(np.uint8).reshape(n, 2)
+    hdr[:, 12:20] = [10, 1, 2, 3, 192, 168, 7, 2]
+    idx = torch.from_numpy((off[:, None] + np.arange(20)[None, :]).reshape(-1)).to(dev)
+    buf[idx] = torch.from_numpy(hdr.reshape(-1)).to(dev)
+    cap = cnt * stride
+    ooff = 12 + np.arange(n, dtype=np.int64) * cap
+    groups = np.stack([np.arange(n) * cnt, np.full(n, cnt)], axis=1).astype(np.uint32)
+    out = torch.zeros(int(ooff[-1] + cap + 16), dtype=torch.uint8, device=dev)
+    rout = torch.zeros(n * pitch + 16, dtype=torch.uint8, device=dev)
+    k = np.tile(np.arange(cnt, dtype=np.int64), n)
+    gi = np.repeat(np.arange(n, dtype=np.int64), cnt)
+    f_src = (off[gi] + 20 + k * per).astype(np.uint64)
+    f_dst = (ooff[gi] + k * stride + 20).astype(np.uint64)
+    f_len = np.minimum(per, tl - k * per).astype(np.uint32) if cnt > 1 else np.full(n, tl, np.uint32)
+    dv = lambda x: torch.from_numpy(x.view(np.int64) if x.dtype == np.uint64 else x.view(np.int32)).to(dev)   # noqa: E731
+    return dict(buf=buf, dd=batch.desc_to_device(batch.make_desc(off, np.full(n, 20 + tl)), dev),
+                grp=torch.from_numpy(groups.reshape(-1).view(np.int32)).to(dev), n_frag=n * cnt, out=out,
+                od=batch.desc_to_device(batch.make_desc(ooff, np.full(n, cap)), dev),
+                of=torch.zeros(16 * n * cnt, dtype=torch.uint8, device=dev), rout=rout,
+                rod=batch.desc_to_device(batch.make_desc(off, np.full(n, 20 + tl)), dev),
+                res=(torch.empty(n, dtype=torch.uint8, device=dev), torch.empty(n, dtype=torch.int32, device=dev),
+                     torch.empty(n, dtype=torch.int16, device=dev)),
+                rres=(torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int16, device=dev),
+                      torch.empty(n, dtype=torch.uint8, device=dev)),
+                f_src=dv(f_src), f_dst=dv(f_dst), f_len=dv(f_len), cnt=cnt)
+
+
+def run_shape(name, n, tl, a, dev, lib):
+    mtu, stride = a.mtu, a.stride
+    sets = [make_set(n, tl, mtu, stride, dev, 900 + i) for i in range(a.rotate)]
+    cnt = sets[0]["cnt"]
+    stream = torch.cuda.current_stream(dev)
+
+    def fragment(s, st):
+        batch.ipv4_fragment_batch(s["buf"], s["dd"], mtu, s["grp"], s["n_frag"], s["out"], s["od"], stride,
+                                  flags=batch.F_WRITE, out_frag=s["of"], stream=st, results=s["res"])
+
+    def reassemble(s, st):
+        batch.ipv4_reassemble_batch(s["out"], s["of"], s["n_frag"], s["grp"], s["rout"], s["rod"], stream=st, results=s["rres"])
+
+    def bare(mode):
+        def f(s, st):
+            assert lib.gather_ceiling_launch(mode, s["buf"].data_ptr(), s["buf"].numel(), s["f_src"].data_ptr(),
+                                             s["f_dst"].data_ptr(), s["f_len"].data_ptr(), s["grp"].data_ptr(), n,
+                                             s["n_frag"], s["out"].data_ptr(), s["out"].numel(),
+                                             ctypes.c_void_p(st.cuda_stream)) == 0
+        return f
+
+    payload = n * tl
+
+    def seq(s, st):
+        assert lib.seq_copy_launch(0, 4, 0, s["rout"].data_ptr(), s["buf"].data_ptr(), payload & ~15,
+                                   ctypes.c_void_p(st.cuda_stream)) == 0
+
+    # the round trip at the timed size, checked once
+    for s in sets:
+        fragment(s, stream)
+        reassemble(s, stream)
+    torch.cuda.synchronize(dev)
+    s = sets[0]
+    ok = bool((s["res"][0] == batch.V_ACCEPT).all() and (s["res"][1] == cnt).all() and (s["rres"][2] == batch.V_ACCEPT).all()
+              and (s["rres"][1] == 0).all() and (s["rres"][0] == tl).all())
+    pitch = (s["buf"].numel() - 16) // n
+    a_in = s["buf"][:n * pitch].view(n, pitch)[:, 32:32 + tl]
+    a_out = s["rout"][:n * pitch].view(n, pitch)[:, 32:32 + tl]
+    same = a_in != a_out
+    same[:, 16:18] = False                                   # the TCP crc the fragment batch stored
+    ok = ok and not bool(same.any())
+    if not ok:
+        raise SystemExit(f"{name}: the fragment / reassemble round trip does not check out at the timed size")
+
+    legs = {"fragment": fragment, "reassemble": reassemble}
+    if lib is not None:
+        legs.update({"bare_scatter_4waves": bare(2), "bare_scatter_flat": bare(3), "seq_copy": seq})
+    graphs = {}
+    for nm, f in legs.items():
+        gph = torch.cuda.CUDAGraph()
+        cs = torch.cuda.Stream(dev)
+        cs.wait_stream(stream)
+        with torch.cuda.stream(cs):
+            with torch.cuda.graph(gph, stream=cs):
+                for s in sets:
+                    f(s, cs)
+        stream.wait_stream(cs)
+        graphs[nm] = gph
+    for _ in range(a.warmup):
+        for gph in graphs.values():
+            gph.replay()
+    torch.cuda.synchronize(dev)
+    times = {nm: [] for nm in legs}
+    # (the bare scatter rounds its stores up past a fragment's end, into the next header: the
+    # fragment leg, which rewrites every header, always runs between it and the reassembly)
+    for _ in range(a.replays):                               # the legs alternate, replay by replay
+        for nm, gph in graphs.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            gph.replay()
+            e1.record(stream)
+            torch.cuda.synchronize(dev)
+            times[nm].append(e0.elapsed_time(e1) * 1e3 / a.rotate)
+    for s in sets:                                           # the timed replays worked on good data
+        if not bool((s["res"][0] == batch.V_ACCEPT).all() and (s["rres"][2] == batch.V_ACCEPT).all()):
+            raise SystemExit(f"{name}: a timed replay did not accept every datagram")
+    # bytes the algorithm needs, from the shapes: read = datagrams + their descriptors / groups /
+    # out descriptors; written = fragments (headers + payload) + fragment descriptors + results
+    read_b = n * (20 + tl) + n * (16 + 8 + 16)
+    written_b = n * (cnt * 20 + tl) + 16 * n * cnt + n * (1 + 4 + 2)
+    r = {"shape": name, "datagrams": n, "transport_bytes": tl, "mtu": mtu, "frag_stride": stride, "fragments": cnt,
+         "rotate": a.rotate, "replays": a.replays, "working_set_bytes_per_set": int(sets[0]["buf"].numel() + sets[0]["out"].numel()),
+         "payload_bytes": payload, "algorithmic_bytes_read": read_b, "algorithmic_bytes_written": written_b,
+         "written_over_algorithmic": round(written_b / (read_b + written_b), 4), "round_trip_checked": ok}
+    for nm, v in times.items():
+        us = float(np.median(v))
+        r[nm + "_us"] = round(us, 2)
+        r[nm + "_us_min_max"] = [round(min(v), 2), round(max(v), 2)]
+        moved = read_b + written_b if nm in ("fragment", "reassemble") else 2 * payload
+        r[nm + "_TBs"] = round(moved / us / 1e6, 3)
+        r[nm + "_fraction_of_8TBs"] = round(moved / (us * 1e-6) / HBM_PEAK, 3)
+    r["fragment_over_reassemble"] = round(r["fragment_us"] / r["reassemble_us"], 3)
+    return r
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shape", default="both", choices=["c3", "9000", "both"])
+    ap.add_argument("--n", type=int, default=0, help="datagrams (0: 4096 x 64512 B, or as many 9000 B ones for the same bytes)")
+    ap.add_argument("--mtu", type=int, default=1500)
+    ap.add_argument("--stride", type=int, default=1504)
+    ap.add_argument("--rotate", type=int, default=3)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--replays", type=int, default=24)
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    if a.replays < 20:
+        raise SystemExit("--replays: at least 20")
+    if not torch.cuda.is_available():
+        raise SystemExit("fragtx_bench.py measures on the GPU: no HIP device here (not measured)")
+    dev = torch.device("cuda:0")
+    lib = None
+    p = os.path.join(ROOT, "tools", "bin", "libgather_ceiling.so")
+    if os.path.exists(p):
+        lib = ctypes.CDLL(p)
+        lib.seq_copy_launch.restype = ctypes.c_int
+        lib.seq_copy_launch.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
+                                        ctypes.c_uint64, ctypes.c_void_p]
+        lib.gather_ceiling_launch.restype = ctypes.c_int
+        lib.gather_ceiling_launch.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64] + [ctypes.c_void_p] * 4 + \
+            [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
+    shapes = []
+    if a.shape in ("c3", "both"):
+        shapes.append(("c3_fragtx", a.n or 4096, 64512))
+    if a.shape in ("9000", "both"):
+        shapes.append(("fragtx_9000", a.n or 4096 * 64512 // 9000, 9000))
+    results = []
+    for name, n, tl in shapes:
+        r = run_shape(name, n, tl, a, dev, lib)
+        print(json.dumps(r), flush=True)
+        results.append(r)
+        torch.cuda.empty_cache()
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump({"device": torch.cuda.get_device_name(0), "results": results}, f, indent=1)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
