@@ -31,7 +31,7 @@ def reasm_path(request):
 
 def gpu_reassemble(buf, d, grp, od, out_size, v6=False, nx=False):
     out = torch.zeros(out_size, dtype=torch.uint8, device="cuda:0")
-    args = (to_dev(buf), to_dev(d.view(np.uint8)), d.size,
+    args = (buf if isinstance(buf, torch.Tensor) else to_dev(buf), to_dev(d.view(np.uint8)), d.size,
             to_dev(np.ascontiguousarray(grp, np.uint32).reshape(-1).view(np.int32)), out, to_dev(od.view(np.uint8)))
     if v6:
         ol, l4, v = batch.ipv6_reassemble_batch(*args, flags=batch.F_NXTHDR_DISPATCH if nx else 0)
@@ -41,13 +41,15 @@ def gpu_reassemble(buf, d, grp, od, out_size, v6=False, nx=False):
     return ol.cpu().numpy().view(np.uint32), l4.cpu().numpy().view(np.uint16), v.cpu().numpy(), out.cpu().numpy()
 
 
-def check(buf, d, grp, od, out_size, v6=False, nx=False):
+def check(buf, d, grp, od, out_size, v6=False, nx=False, far=None):
+    """Oracle on (buf, d) against the GPU on the same -- or on far = (device buffer, descriptors):
+    the same fragments laid out elsewhere."""
     out_o = np.zeros(out_size, np.uint8)
     if v6:
         wl, w4, wv = O.ipv6_reassemble(buf, d, grp, out_o, od, nxthdr_dispatch=nx)
     else:
         wl, w4, wv = O.ipv4_reassemble(buf, d, grp, out_o, od)
-    gl, g4, gv, out_g = gpu_reassemble(buf, d, grp, od, out_size, v6, nx)
+    gl, g4, gv, out_g = gpu_reassemble(*(far or (buf, d)), grp, od, out_size, v6, nx)
     np.testing.assert_array_equal(gv, wv)
     np.testing.assert_array_equal(gl, wl)
     np.testing.assert_array_equal(g4, w4)
@@ -391,3 +393,101 @@ def test_flat_grid_two_fragments_a_lane(v6, reasm_path):
         batch.set_reasm_flat(2)
         wl2, wv2 = check(buf, d, grp, od, size, v6=v6)
         assert (wv2 == wv).all() and (wl2 == wl).all()
+
+
+FAR_SIZE = 9 << 28                                       # 2.25 GiB
+FAR_BANDS = (4096, 1100 << 20, 2200 << 20)               # near 0, 1.1 GiB and 2.2 GiB
+
+
+def _far_case(v6):
+    """A dozen datagrams (fragment payloads 8, 552 / 520 and 1480 / 1448) on a compact buffer, one
+    of them with a true retransmission, and the same fragments laid out for a FAR_SIZE buffer:
+    arrival j (the descriptor index) goes to band j % 3, packed there with a seeded 0-15 byte
+    jitter.  Datagram 3 (258 fragments) also gets copies of three fragments as its arrivals 244, 248
+    and 252: on the 4-wave workgroup path wave 0's fragments 61-63, the last of its first block of
+    64, so the pair (60, 64) spans two metadata blocks and, lying in two bands, is split.  Returns (buf, off, far_off, flen, grp, lens, (copy, original))."""
+    rng = np.random.default_rng(900 + v6)
+    parts = [(8, [7, 8, 200, 2064]), (520 if v6 else 552, [2959, 12000, 7, 5000]),
+             (1448 if v6 else 1480, [12000, 2959, 8, 30000])]
+    bufs, offs, flens, grps, lens, nf, nb = [], [], [], [], [], 0, 0
+    for k, (pl, ls) in enumerate(parts):
+        if v6:
+            ls = [x // 8 * 8 + 8 for x in ls]
+            b, o, n, g = synth.ipv6_fragments(ls, seed=60 + k, proto=17, frag_payload=pl)
+        else:
+            b, o, n, g = synth.ipv4_fragments(ls, seed=60 + k, proto=17, frag_payload=pl)
+        g = g.copy()
+        g[:, 0] += nf
+        bufs.append(b)
+        offs.append(o + np.uint64(nb))
+        flens.append(n)
+        grps.append(g)
+        lens += ls
+        nf += o.size
+        nb += b.size
+    buf, off, flen, grp = np.concatenate(bufs), np.concatenate(offs), np.concatenate(flens), np.concatenate(grps)
+    # the retransmission: a copy of datagram 5's second arrival, arriving right behind it
+    first = int(grp[5, 0])
+    orig = first + 1
+    o, n = int(off[orig]), int(flen[orig])
+    off = np.insert(off, orig + 1, buf.size)
+    flen = np.insert(flen, orig + 1, n)
+    buf = np.concatenate([buf, buf[o:o + n], np.zeros(16, np.uint8)])
+    grp[5, 1] += 1
+    grp[6:, 0] += 1
+    first = int(grp[3, 0])
+    for k in (244, 248, 252):                            # (behind their originals: not kept)
+        o, n = int(off[first + k - 200]), int(flen[first + k - 200])
+        off = np.insert(off, first + k, buf.size)
+        flen = np.insert(flen, first + k, n)
+        buf = np.concatenate([buf, buf[o:o + n], np.zeros(16, np.uint8)])
+        grp[3, 1] += 1
+        grp[4:, 0] += 1
+    band = np.arange(off.size) % 3
+    far_off = np.zeros(off.size, np.uint64)
+    pos = list(FAR_BANDS)
+    for j in range(off.size):
+        far_off[j] = pos[band[j]] + int(rng.integers(0, 16))
+        pos[band[j]] = int(far_off[j]) + int(flen[j]) + 14
+    assert pos[0] < FAR_BANDS[1] and pos[1] < FAR_BANDS[2] and pos[2] + 64 <= FAR_SIZE
+    return buf, off, far_off, flen, grp, lens, (orig + 4, orig + 3)
+
+
+@pytest.mark.parametrize("v6", [False, True])
+def test_reassembly_far_apart(v6):
+    """A datagram's fragments more than 1 GiB apart in a batch buffer over 2 GiB: a gather pair
+    that no single window holds is split (both paths), and a header outside the planner's / the
+    gather wave's header window is parsed from byte loads.  Consecutive arrivals lie in different
+    bands of the buffer, a first arrival in the top band has the rest of its datagram more than
+    1 GiB below it, one in the bottom band has fragments past 2 GiB, and a true retransmission
+    lies in another band than its original.  Every verdict, length, checksum and reassembled byte
+    against the oracle on the same fragments packed densely."""
+    buf, off, far_off, flen, grp, lens, (copy, orig) = _far_case(v6)
+    assert 100 < off.size < 400 and len(lens) == 12
+    GiB = 1 << 30
+    band = np.searchsorted(np.array(FAR_BANDS[1:], np.uint64), far_off, side="right")
+    assert (band[1:] != band[:-1]).all()                 # consecutive arrivals alternate bands
+    fo = far_off.astype(np.int64)
+    top = [g for g, (f, c) in enumerate(grp.tolist()) if band[f] == 2 and c > 1 and
+           (fo[f] - fo[f + 1:f + c] > GiB).sum() >= c // 2]
+    bottom = [g for g, (f, c) in enumerate(grp.tolist()) if band[f] == 0 and (fo[f:f + c] > 2 * GiB).any()]
+    assert top and bottom
+    assert band[copy] != band[orig] and abs(int(fo[copy]) - int(fo[orig])) > GiB
+    f3 = int(grp[3, 0])                                  # wave 0's pair (60, 64) of 4 waves: two blocks, two bands
+    assert grp[3, 1] > 256 and band[f3 + 240] != band[f3 + 256]
+    assert all(off[f3 + k] >= off[:f3].max() and flen[f3 + k] == flen[f3 + k - 200] for k in (244, 248, 252))
+    assert flen[copy] == flen[orig] and 5 in [g for g, (f, c) in enumerate(grp.tolist()) if f <= orig < f + c]
+    d, far = G.ipv4_desc(off, flen), G.ipv4_desc(far_off, flen)
+    od, size = layout(lens, shift=8 if v6 else 4, hdr=40 if v6 else 20)
+    big = torch.zeros(FAR_SIZE, dtype=torch.uint8, device="cuda:0")
+    for b in range(3):                                   # one upload per band
+        idx = np.flatnonzero(band == b)
+        lo, hi = int(fo[idx].min()), int((fo[idx] + flen[idx]).max())
+        img = np.zeros(hi - lo, np.uint8)
+        for j in idx:
+            img[int(fo[j]) - lo:int(fo[j]) - lo + int(flen[j])] = buf[int(off[j]):int(off[j]) + int(flen[j])]
+        big[lo:hi] = torch.from_numpy(img).to("cuda:0")
+    wl, wv = check(buf, d, grp, od, size, v6=v6, far=(big, far))
+    assert (wv != 8).all() and (wl == np.array(lens)).all()
+    del big
+    torch.cuda.empty_cache()
