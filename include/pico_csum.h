@@ -53,7 +53,8 @@ extern "C" {
  *      is rejected with -EINVAL); the forwarding batch takes the host's link addresses and a
  *      carried state (pico_ipv4_pre_forward_checks in full);
  *   4: pico_csum_release_thread_scratch; the reassembly's flat-grid scratch is freed at thread exit;
- *   4 (added, no bump): pico_ipv4_fragment_batch_dev -- a new entry point breaks no caller. */
+ *   4 (added, no bump): pico_ipv4_fragment_batch_dev -- a new entry point breaks no caller;
+ *   4 (added, no bump): pico_tcp_segment_batch_dev -- likewise. */
 #define PICO_CSUM_ABI_VERSION 4
 
 /* picoTCP pico_err values used here (include/pico_protocol.h:27,31,38 + ENODEV) */
@@ -101,7 +102,8 @@ struct pico_csum_desc {
  *   forwarding:            ACCEPT, MALFORMED, EXPIRED, LOCAL_SRC, DUPLICATE
  *   NAT:                   ACCEPT, MALFORMED, FRAG, UNTOUCHED
  *   reassembly:            ACCEPT, L4_BAD, MALFORMED
- *   fragmentation (TX):    ACCEPT, MALFORMED */
+ *   fragmentation (TX):    ACCEPT, MALFORMED
+ *   TCP segmentation (TX): ACCEPT, MALFORMED */
 #define PICO_CSUM_V_ACCEPT    1u  /* delivered to the transport and every checksum the reference
                                      checks passes: hand the frame on (a stack built with CRC=0
                                      need not check it again) */
@@ -414,6 +416,71 @@ int pico_ipv4_fragment_batch_dev(const void *d_base, uint64_t base_len, const st
                                  uint64_t out_len, const struct pico_csum_desc *d_out_desc, uint32_t frag_stride,
                                  struct pico_csum_desc *d_out_frag, uint32_t *d_out_count, uint16_t *d_out_transport,
                                  uint8_t *d_verdict, uint32_t flags, void *stream);
+
+/* TCP send segmentation (what a NIC calls TSO): one header template and one long payload per
+ * connection become the segment-sized frames of a pico_socket_write, each with its own IPv4 header
+ * checksum and TCP checksum, in one pass that reads each payload byte once.  The batch form of
+ * pico_socket_xmit / pico_socket_xmit_one (stack/pico_socket.c:1322-1358, :1070-1127: a frame per
+ * `space` bytes, memcpy of the payload), pico_tcp_push (modules/pico_tcp.c:3127-3157: seq =
+ * snd_last + 1, snd_last += payload_len), pico_tcp_output / tcp_add_options_frame (:2924-2998,
+ * :633-660), tcp_send (:968-985: crc = short_be(pico_tcp_checksum(f))) and pico_ipv4_frame_push
+ * (modules/pico_ipv4.c:1039-1079: len, id = ipv4_progressive_id++, frag = DF, pico_ipv4_checksum);
+ * the reference touches every payload byte twice (memcpy, checksum) and every header twice.  The
+ * rule below reproduces, byte for byte, the data segments the compiled reference emits for a write
+ * within one millisecond of its clock, or on a connection without the timestamp option
+ * (tests/golden/make_ref_tcpseg.py, tests/test_ref_tcpseg.py).  The TX batches above checksum frames the host has built one
+ * by one; this one builds them.
+ *   d_stream[g] one send unit: desc.off -> a network header, the TCP header and the payload, contiguous;
+ *              desc.len = the byte count of all of it (the payload may be far longer than 65535);
+ *              desc.seed = `per`, the payload bytes a segment (the reference's `space`,
+ *              pico_socket_xmit_avail_space: the socket's MSS minus the option overhead -- per
+ *              connection, so per stream).  The version nibble selects the family: IPv4 with IHL 5
+ *              and proto 6 (N = 20), or IPv6 with nxthdr 6 and no extension header (N = 40).  thl =
+ *              4 (TCP byte 12 >> 4), 20..60; H = N + thl; P = desc.len - H.
+ *   split      count = max(1, ceil(P / per)) (P = 0: one bare-header frame).  Segment k carries
+ *              payload bytes [k per, min((k + 1) per, P)) behind a copy of the H template bytes with
+ *              IPv4: len = H + payload, id = template id + k (mod 2^16), frag = 40 00 (DF,
+ *              pico_ipv4.c:1059), crc = pico_ipv4_checksum; IPv6: payload length (bytes 4-5) = thl +
+ *              payload; TCP: seq = template seq + k per (mod 2^32), crc = pico_tcp_checksum with the
+ *              pseudo header of the template's addresses, proto 6 and length thl + payload (struct
+ *              pico_ipv4_pseudo_hdr / pico_ipv6_pseudo_hdr).  Everything else -- ports, ack, flags,
+ *              window, urgent pointer, options, tos, ttl / hop limit, addresses, flow label -- is the
+ *              template's on every segment.  The reference puts PSH|ACK on every segment too (PSH is
+ *              not moved to the last); it stamps each segment's timestamp option with the clock's
+ *              millisecond as it sends it (tcp_add_options_frame: tsval = TCP_TIME), the batch copies
+ *              the template's: per-segment options are out of scope, and a later tsval means a new
+ *              send unit.  The template's IPv4 len, frag and crc, its IPv6 payload length and its TCP
+ *              crc are not read.
+ *   d_out_desc[] per stream: output region in d_out (off any alignment, len = capacity).  Segment k
+ *              starts at off + k seg_stride; seg_stride a multiple of 4, >= 40 (else -EINVAL).  off + H
+ *              = 0 mod 16 with a stride that is a multiple of 16 puts every payload on a 16-byte
+ *              line (whole-line stores; off = 12 mod 16 for IPv4 with thl 32).
+ *   d_groups[] 2 uint32 per stream, the fragmentation batch's layout, read-only: first slot in
+ *              d_out_seg, slots reserved.  d_out_seg[first + k] = {segment k's offset in d_out, H +
+ *              payload, 0}; reserved slots past count = {0, 0, 0}.  d_out and d_out_seg go to
+ *              pico_ipv4_checksum_batch_dev / pico_ipv6_checksum_batch_dev as they are (RX mode:
+ *              every frame ACCEPT, both results 0; IPv6 with PICO_CSUM_F_NXTHDR_DISPATCH, the default
+ *              dispatch reads the source address's second byte).
+ *   d_out_count[g]     segments emitted (0 when MALFORMED)
+ *   d_verdict[g]       ACCEPT, or MALFORMED = no byte of the region is written, count 0, slots {0, 0,
+ *              0}; checked in an order that never reads past desc.len: a stream past base_len, len <
+ *              1, a version other than 4 / 6, len < N, IHL != 5, proto / nxthdr != 6, len < N + 20,
+ *              thl < 20, len < H, per = 0, a frame length that does not fit its 16-bit field (IPv4: H +
+ *              min(per, P) > 65535, IPv6: thl + min(per, P) > 65535), H + min(per, P) > seg_stride,
+ *              fewer reserved slots than count, slots past n_seg (then no slot is written either), an
+ *              output region too small for (count - 1) seg_stride + the last frame or past out_len.
+ * No byte outside [d_out_desc[g].off, + len) is written, and inside it only the frames' own bytes
+ * (gaps between frames keep their contents).  Reads follow the whole-16-byte-block rule above.
+ * d_out_seg, d_out_count and d_verdict may each be NULL.  Regions and slot ranges of different
+ * streams must not overlap.  flags is reserved: anything but 0 is -EINVAL.  The host keeps the TCP
+ * state (INTEGRATION.md 5a''): after the call snd_last advances by P and the id counter by count.
+ * One launch, one workgroup per stream (four waves; one wave in batches of 3072 streams or more that
+ * reserve at most 16 slots a stream on average); results never depend on the launch shape. */
+int pico_tcp_segment_batch_dev(const void *d_base, uint64_t base_len, const struct pico_csum_desc *d_stream,
+                               uint32_t n_stream, const uint32_t *d_groups, uint32_t n_seg, void *d_out,
+                               uint64_t out_len, const struct pico_csum_desc *d_out_desc, uint32_t seg_stride,
+                               struct pico_csum_desc *d_out_seg, uint32_t *d_out_count, uint8_t *d_verdict,
+                               uint32_t flags, void *stream);
 
 /* ---------------------------------------------------------------- layer 3 */
 

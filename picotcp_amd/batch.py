@@ -364,6 +364,49 @@ def ipv4_fragment_batch(base: torch.Tensor, dgram_desc: torch.Tensor, mtu: int, 
     return v, cnt, l4
 
 
+def tcp_segment_batch(base: torch.Tensor, stream_desc: torch.Tensor, groups: torch.Tensor, n_seg: int,
+                      out: torch.Tensor, out_desc: torch.Tensor, seg_stride: int, flags: int = 0,
+                      out_seg: torch.Tensor | None = None, stream=None, results=None):
+    """TCP send segmentation + every frame's IPv4 header checksum and TCP checksum in one pass
+    (pico_socket_xmit, pico_socket.c:1322-1358; pico_tcp_push / tcp_send, pico_tcp.c:3127-3157, :968-985;
+    pico_ipv4_frame_push, pico_ipv4.c:1039-1079).  stream_desc = one send unit per descriptor: off ->
+    IPv4 (IHL 5) or IPv6 header + TCP header + payload, len = all of it, seed = payload bytes a
+    segment; groups = uint32 (first slot, slots reserved) pairs per stream (int32 tensor of 2*n), out =
+    uint8 device buffer; segment k of stream g is written at out_desc[g].off + k*seg_stride with its
+    own len / id + k / seq + k*per and checksums.  out_seg (uint8 tensor of 16*n_seg bytes, or None)
+    receives the segments' descriptors -- with `out`, the input of ipv4_checksum_batch /
+    ipv6_checksum_batch.  flags: reserved, 0.  Returns (verdict uint8[n], count int32[n]); `results`
+    may pass that pair preallocated, either of them None to skip it."""
+    for t, nm in ((base, "base"), (stream_desc, "stream_desc"), (groups, "groups"), (out, "out"), (out_desc, "out_desc")):
+        _require_device(t, nm)
+        if t.device != base.device:
+            raise ValueError(f"{nm} is on {t.device}, the batch on {base.device}")
+    _require_u8(base, "base")
+    _require_u8(out, "out")
+    n = groups.numel() // 2
+    if groups.element_size() != 4 or not groups.is_contiguous():
+        raise ValueError("groups must be a contiguous 32-bit tensor of (first, reserved) pairs")
+    if stream_desc.numel() * stream_desc.element_size() < 16 * n or out_desc.numel() * out_desc.element_size() < 16 * n:
+        raise ValueError("descriptor tensor shorter than its count")
+    dev = base.device
+    if out_seg is not None:
+        _require_device(out_seg, "out_seg")
+        if out_seg.device != dev or not out_seg.is_contiguous() or out_seg.numel() * out_seg.element_size() < 16 * n_seg:
+            raise ValueError("out_seg must be a contiguous tensor of n_seg 16-byte descriptors on the batch's device")
+    if results is None:
+        results = (torch.empty(n, dtype=torch.uint8, device=dev), torch.empty(n, dtype=torch.int32, device=dev))
+    v, cnt = results
+    for t, nm, sz in ((v, "verdict", 1), (cnt, "count", 4)):
+        if t is not None:
+            _check_out(t, n, nm, dev, sz)
+    lib = _lib.load()
+    _lib.check("pico_tcp_segment_batch_dev",
+               lib.pico_tcp_segment_batch_dev(_ptr(base), base.numel(), _ptr(stream_desc), n, _ptr(groups), n_seg,
+                                              _ptr(out), out.numel(), _ptr(out_desc), seg_stride, _ptr(out_seg),
+                                              _ptr(cnt), _ptr(v), flags, _stream_handle(stream)))
+    return v, cnt
+
+
 STREAM_OFF = 0xFF
 
 

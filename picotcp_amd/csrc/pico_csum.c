@@ -7,7 +7,8 @@
  * Layer 2: argument checking + launch-shape choice for the batched HIP
  *          kernels (pico_csum_k_raw.hip: uniform rings; pico_csum_k_sorted.hip:
  *          every descriptor batch and the forwarding step; pico_csum_k_frag.hip:
- *          reassembly), reached through the thin extern "C" launchers declared below.
+ *          reassembly; pico_csum_k_fragtx.hip: TX fragmentation; pico_csum_k_tcpseg.hip: TCP send
+ *          segmentation), reached through the thin extern "C" launchers declared below.
  * Layer 3: host-resident batches: pinned staging, two streams, chunked
  *          H2D -> kernel -> D2H overlap.
  */
@@ -49,6 +50,9 @@ int pico_csum_launch_fragment(const void *base, uint64_t base_len, const void *d
                               const uint32_t *groups, uint32_t n_frag, void *out, uint64_t out_len, const void *out_desc,
                               uint32_t stride, void *o_frag, uint32_t *o_count, uint16_t *o_l4, uint8_t *verdict,
                               uint32_t flags, void *stream);
+int pico_csum_launch_tcp_segment(const void *base, uint64_t base_len, const void *strm, uint32_t n_stream,
+                                 const uint32_t *groups, uint32_t n_seg, void *out, uint64_t out_len, const void *out_desc,
+                                 uint32_t stride, void *o_seg, uint32_t *o_count, uint8_t *verdict, void *stream);
 
 /* ------------------------------------------------------------------ errors */
 
@@ -627,6 +631,33 @@ int pico_ipv4_fragment_batch_dev(const void *d_base, uint64_t base_len, const st
                                                    out_len, d_out_desc, frag_stride, d_out_frag, d_out_count,
                                                    d_out_transport, d_verdict, flags, stream),
                          "pico_ipv4_fragment_batch_dev");
+}
+
+int pico_tcp_segment_batch_dev(const void *d_base, uint64_t base_len, const struct pico_csum_desc *d_stream,
+                               uint32_t n_stream, const uint32_t *d_groups, uint32_t n_seg, void *d_out,
+                               uint64_t out_len, const struct pico_csum_desc *d_out_desc, uint32_t seg_stride,
+                               struct pico_csum_desc *d_out_seg, uint32_t *d_out_count, uint8_t *d_verdict,
+                               uint32_t flags, void *stream)
+{
+    int rc;
+    if (n_stream == 0)
+        return 0;
+    if (!d_base || !d_stream || !d_groups || !d_out || !d_out_desc)
+        return fail(PICO_CSUM_EINVAL, "NULL buffer");
+    if (((uintptr_t)d_stream & 15u) != 0 || ((uintptr_t)d_out_desc & 15u) != 0 || ((uintptr_t)d_out_seg & 15u) != 0)
+        return fail(PICO_CSUM_EINVAL, "descriptor arrays must be 16-byte aligned");
+    if (((uintptr_t)d_groups & 3u) != 0 || ((uintptr_t)d_out_count & 3u) != 0)
+        return fail(PICO_CSUM_EINVAL, "d_groups and d_out_count must be 4-byte aligned");
+    if (flags != 0)
+        return fail(PICO_CSUM_EINVAL, "unknown flags 0x%x%s (none is defined for this batch)", flags, retired_note(flags));
+    if (seg_stride < 40u || (seg_stride & 3u) != 0)
+        return fail(PICO_CSUM_EINVAL, "seg_stride %u: a multiple of 4, at least 40 (the shortest frame)", seg_stride);
+    if ((rc = need_device()) != 0)
+        return rc;
+    return launch_status(pico_csum_launch_tcp_segment(d_base, base_len, d_stream, n_stream, d_groups, n_seg, d_out,
+                                                      out_len, d_out_desc, seg_stride, d_out_seg, d_out_count,
+                                                      d_verdict, stream),
+                         "pico_tcp_segment_batch_dev");
 }
 
 /* ------------------------------------------------------------------ layer 3 */

@@ -1,5 +1,6 @@
 // pico_csum_dev.h -- device helpers shared by the gfx950 kernel TUs of libpicocsum
-// (pico_csum_k_raw.hip, pico_csum_k_sorted.hip, pico_csum_k_frag.hip, pico_csum_k_fragtx.hip).
+// (pico_csum_k_raw.hip, pico_csum_k_sorted.hip, pico_csum_k_frag.hip, pico_csum_k_fragtx.hip,
+// pico_csum_k_tcpseg.hip).
 // Header-only, internal; everything lives in an anonymous namespace (one copy per TU).
 //
 // The kernels of picoTCP's Internet checksum.

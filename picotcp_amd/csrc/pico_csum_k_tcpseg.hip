@@ -1,0 +1,277 @@
+// pico_csum_k_tcpseg.hip -- TCP send segmentation (what a NIC calls TSO): one header template and one
+// long payload per connection scattered into segment-sized frames, every frame with its own IPv4
+// header checksum and TCP checksum, in one pass that reads each payload byte once -- and its
+// launcher.  The TCP sibling of the fragmentation scatter (pico_csum_k_fragtx.hip), whose output
+// conventions and 16-byte unit scheme it keeps.  Helpers and the arithmetic contract: pico_csum_dev.h.
+//
+// Reference: pico_socket_xmit (stack/pico_socket.c:1322-1358) loops pico_socket_xmit_one
+// (:1070-1127: a frame per `space` bytes, memcpy of the payload); pico_tcp_push
+// (modules/pico_tcp.c:3127-3157: seq = snd_last + 1, snd_last += payload_len); pico_tcp_output
+// (:2924-2998) with tcp_add_options_frame (:633-660); tcp_send (:968-985: ports, PSH|ACK, ack, rwnd,
+// crc = short_be(pico_tcp_checksum(f))); pico_ipv4_frame_push (modules/pico_ipv4.c:1039-1079: len,
+// id = ipv4_progressive_id++, frag = DF, pico_ipv4_checksum).  The reference touches every payload
+// byte twice (memcpy, pico_tcp_checksum) and every header twice.
+//
+// One workgroup per stream (4 waves; 1 wave in large batches of short streams, see the launch
+// shapes below); every check is made before the first store (a MALFORMED stream writes nothing
+// into its region):
+//   1. the template, one lane per 32-bit word of its H = N + thl bytes (H <= 100: 25 lanes): the
+//      word sums of the IPv4 header without len / id / frag / crc, of the addresses (the pseudo
+//      header's address part) and of the TCP header without seq / crc, once per stream;
+//   2. wave w takes the segment pairs w, w + 4, ... (one wave: every pair): segments 2j and
+//      2j + 1.  The payload moves in 16-byte units on the OUTPUT's 16-byte lines (a segment whose payload starts o bytes into a
+//      line has units [0, (o + payload + 15) / 16)), the two segments' units in one index space
+//      (two 1448-byte payloads fill 3 x 64 lanes): one byte-unaligned 16-byte load per unit (the
+//      source / destination relative alignment changes from segment to segment unless stride - per
+//      keeps it), one aligned 16-byte store per whole unit, byte stores for the bytes of a
+//      segment's first and last unit.  The one unit whose 16 bytes would run past the last 16-byte
+//      block that overlaps the stream is read byte by byte (the whole-block read rule of
+//      include/pico_csum.h).  Every unit's bytes enter its OWN segment's sum on the way (v_dot2; an
+//      odd o swaps the bytes of each 16-bit half first: the pairing is relative to the segment's
+//      payload start, whatever the parity of k per): two accumulators per lane, two wave
+//      reductions (DPP) per pair -- no LDS, no barrier;
+//   3. behind the reductions the wave writes both headers once, complete: the template's words
+//      with len, id + k, DF and pico_ipv4_checksum (IPv4) or the payload length (IPv6), seq +
+//      k per, and pico_tcp_checksum = the template's sums + the segment's own len / seq words + its
+//      payload sum.  A 32-bit store per word where the frame is 4-byte aligned, byte stores
+//      otherwise.
+#include "pico_csum_dev.h"
+
+namespace {
+
+struct TcpSegArgs {
+    const uint8_t* base;
+    uint64_t base_len;
+    const pico_csum_desc_dev* strm;     // per stream: template + payload (off, len), seed = payload bytes a segment
+    uint32_t n_stream;
+    const uint32_t* grp;                // 2 per stream: first slot, slots reserved
+    uint32_t n_seg;
+    uint32_t stride;
+    uint8_t* out;
+    uint64_t out_len;
+    const pico_csum_desc_dev* odesc;    // per stream: output region (off, capacity)
+    pico_csum_desc_dev* o_seg;
+    uint32_t* o_count;
+    uint8_t* verdict;
+};
+
+// Launch shapes, the fragmentation kernel's two.  Four waves per stream and three
+// 64-unit slots per step; large batches of short streams -- TCPSEG_SHORT_MIN streams or more, at
+// most TCPSEG_SHORT_SEGS slots reserved a stream on average -- one wave per stream and
+// TCPSEG_SHORT_U slots per step: there the per-stream latency chain (descriptor, template, first
+// loads, reduction, headers) is what occupancy has to hide.  Measured for this kernel
+// (profiles/tcpseg/ab_shapes.txt): the two shapes and TCPSEG_SHORT_U = 1 / 2 / 3 at ONE point, 29360
+// streams of 7 segments.  NOT measured for it: the two thresholds where the launcher changes shape;
+// they are the fragmentation kernel's values, taken over as they stand.
+constexpr uint32_t TCPSEG_SHORT_MIN = 3072u;
+constexpr uint32_t TCPSEG_SHORT_SEGS = 16u;
+constexpr uint32_t TCPSEG_SHORT_U = 1u;
+
+__device__ __forceinline__ uint32_t bswap16(uint32_t v) { return ((v & 0xFFu) << 8) | ((v >> 8) & 0xFFu); }
+
+__device__ __forceinline__ uint4 load_una(const uint8_t* p) {
+    uint4 v;
+    __builtin_memcpy(&v, p, 16);
+    return v;
+}
+
+__device__ __forceinline__ uint32_t word_of(const uint4& v, uint32_t q) { return sel4(q, v.x, v.y, v.z, v.w); }
+
+__device__ __forceinline__ uint32_t halves(uint32_t w, bool lo, bool hi) {
+    return (lo ? w & 0xFFFFu : 0u) + (hi ? w >> 16 : 0u);
+}
+
+// TSG_WAVES waves per stream, TSG_U 64-unit slots per step (3: two 1448-byte payloads)
+template <uint32_t TSG_WAVES, uint32_t TSG_U>
+__global__ __launch_bounds__(64 * TSG_WAVES) void tcp_segment_kernel(TcpSegArgs p) {
+    const uint32_t g = blockIdx.x;
+    if (g >= p.n_stream) return;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+    const pico_csum_desc_dev d = p.strm[g], od = p.odesc[g];
+    const uint32_t first = p.grp[2 * g], reserved = p.grp[2 * g + 1];
+    const uint32_t per = d.seed;
+
+    // ---- checks (workgroup-uniform, in an order that never reads past d.len): nothing is stored
+    // for a stream that fails one
+    const bool slots_in = first <= p.n_seg && reserved <= p.n_seg - first;
+    bool bad = d.off > p.base_len || d.len > p.base_len - d.off || d.len < 1u;
+    const uint8_t* h = p.base + d.off;
+    uint32_t N = 20u, thl = 20u;
+    bool v6 = false;
+    if (!bad) {
+        const uint32_t b0 = h[0];
+        v6 = (b0 >> 4) == 6u;
+        N = v6 ? 40u : 20u;
+        bad = !(v6 || (b0 >> 4) == 4u) || d.len < N;
+        if (!bad) bad = v6 ? (uint32_t)h[6] != 6u : ((b0 & 15u) != 5u || (uint32_t)h[9] != 6u);
+        bad = bad || d.len < N + 20u;
+        if (!bad) {
+            thl = 4u * ((uint32_t)h[N + 12u] >> 4);
+            bad = thl < 20u || d.len < N + thl;
+        }
+    }
+    const uint32_t H = N + thl;
+    const uint32_t P = bad ? 0u : d.len - H;
+    bad = bad || per == 0u;
+    const uint32_t seg0 = min(per, P);                              // the longest segment's payload
+    bad = bad || (uint64_t)(v6 ? thl : H) + seg0 > 65535u || (uint64_t)H + seg0 > p.stride;
+    const uint32_t count = bad ? 0u : (P <= per ? 1u : (uint32_t)(((uint64_t)P + per - 1u) / per));
+    const uint32_t last_pl = bad ? 0u : (uint32_t)(P - (uint64_t)(count - 1u) * per);
+    const uint64_t need = bad ? 0u : (uint64_t)(count - 1u) * p.stride + H + last_pl;
+    bad = bad || reserved < count || !slots_in || od.off > p.out_len || od.len > p.out_len - od.off || need > od.len;
+
+    if (p.o_seg && slots_in) {                                      // the group's slots: descriptors, then {0, 0, 0}
+        for (uint32_t k = tid; k < reserved; k += 64u * TSG_WAVES) {
+            pico_csum_desc_dev f{0, 0, 0};
+            if (!bad && k < count) {
+                f.off = od.off + (uint64_t)k * p.stride;
+                f.len = H + (k + 1u < count ? per : last_pl);
+            }
+            p.o_seg[first + k] = f;
+        }
+    }
+    if (tid == 0) {
+        if (p.o_count) p.o_count[g] = bad ? 0u : count;
+        if (p.verdict) p.verdict[g] = (uint8_t)(bad ? V_MALFORMED : V_ACCEPT);
+    }
+    if (bad) return;
+
+    // ---- 1. the template: lane l holds its 32-bit word l (little-endian, as it lies in memory)
+    const uint32_t nw = H >> 2, tw0 = N >> 2;                       // words; the TCP header's first
+    uint32_t tw = 0;
+    if (lane < nw) __builtin_memcpy(&tw, h + 4u * lane, 4);
+    const uint32_t j = lane - tw0;                                  // the word's place in the TCP header
+    // IPv4 header without len (word 0 high), id / frag (word 1), crc (word 2 high)
+    const uint32_t n_part = !v6 && lane < 5u ? halves(tw, lane != 1u, lane >= 3u) : 0u;
+    const uint32_t a_part = (v6 ? lane >= 2u && lane < 10u : lane >= 3u && lane < 5u) ? halves(tw, true, true) : 0u;
+    // TCP header without seq (word 1) and crc (word 4 low)
+    const uint32_t t_part = lane >= tw0 && lane < nw ? halves(tw, j != 1u && j != 4u, j != 1u) : 0u;
+    const uint32_t nsum = (uint32_t)__builtin_amdgcn_readlane((int)group_sum<64>(n_part), 63);
+    // the pseudo header's constant part (struct pico_ipv4_pseudo_hdr / pico_ipv6_pseudo_hdr as LE
+    // words: the addresses, proto 6) and the TCP header's
+    const uint32_t csum = (uint32_t)__builtin_amdgcn_readlane((int)group_sum<64>(a_part + t_part), 63) + (6u << 8);
+    const uint32_t id0 = bswap16((uint32_t)__builtin_amdgcn_readlane((int)tw, 1) & 0xFFFFu);
+    const uint32_t seq0 = __builtin_bswap32((uint32_t)__builtin_amdgcn_readlane((int)tw, (int)(tw0 + 1u)));
+
+    // ---- 2. scatter + per-segment sums, 3. headers
+    const uint64_t S = reinterpret_cast<uint64_t>(h) + H;                            // the payload
+    const uint64_t a1 = (reinterpret_cast<uint64_t>(h) + d.len + 15u) & ~(uint64_t)15;   // end of its last 16-byte block
+    const uint64_t D = reinterpret_cast<uint64_t>(p.out) + od.off;                   // segment 0's header
+    const uint32_t npair = (count + 1u) >> 1;
+    for (uint32_t jp = wv; jp < npair; jp += TSG_WAVES) {
+        const uint32_t kA = 2u * jp, kB = kA + 1u;
+        const bool hasB = kB < count;
+        const uint32_t plA = kA + 1u < count ? per : last_pl, plB = hasB ? (kB + 1u < count ? per : last_pl) : 0u;
+        const uint64_t dA = D + (uint64_t)kA * p.stride, dB = D + (uint64_t)kB * p.stride;
+        const uint32_t oA = (uint32_t)(dA + H) & 15u, oB = (uint32_t)(dB + H) & 15u;
+        const uint32_t nuA = (oA + plA + 15u) >> 4, nuB = hasB ? (oB + plB + 15u) >> 4 : 0u, nt = nuA + nuB;
+        const uint64_t sA = S + (uint64_t)kA * per, sB = S + (uint64_t)kB * per;
+
+        uint32_t accA = 0, accB = 0;
+        for (uint32_t x0 = 0; x0 < nt; x0 += 64u * TSG_U) {
+            uint4 c[TSG_U];
+            uint32_t lo[TSG_U], hi[TSG_U], od16[TSG_U];
+            bool inb[TSG_U];
+            uint64_t dst[TSG_U];
+#pragma unroll
+            for (uint32_t q = 0; q < TSG_U; ++q) {
+                const uint32_t x = x0 + 64u * q + lane;
+                inb[q] = x >= nuA;
+                const uint32_t u = inb[q] ? x - nuA : x, o = inb[q] ? oB : oA, pl = inb[q] ? plB : plA;
+                // the unit's segment bytes are [lo, hi) of its 16
+                lo[q] = u == 0u ? o : 0u;
+                hi[q] = x < nt ? (uint32_t)min(16, max((int)(o + pl) - (int)(16u * u), 0)) : 0u;
+                od16[q] = o & 1u;
+                dst[q] = (inb[q] ? dB : dA) + H + 16u * u - o;                       // 16-byte aligned
+                const uint64_t src = (inb[q] ? sB : sA) + 16u * u - o;               // >= the template's byte 25
+                c[q] = make_uint4(0, 0, 0, 0);
+                if (hi[q] > lo[q]) {
+                    if (src + 16u <= a1) {
+                        c[q] = load_una(reinterpret_cast<const uint8_t*>(src));
+                    } else {                                                         // the stream's last unit
+                        uint32_t w[4] = {0, 0, 0, 0};
+                        for (uint32_t i = lo[q]; i < hi[q]; ++i) {
+                            const uint32_t byte = (uint32_t)*reinterpret_cast<const uint8_t*>(src + i) << (8u * (i & 3u));
+                            w[0] |= (i >> 2) == 0u ? byte : 0u;
+                            w[1] |= (i >> 2) == 1u ? byte : 0u;
+                            w[2] |= (i >> 2) == 2u ? byte : 0u;
+                            w[3] |= (i >> 2) == 3u ? byte : 0u;
+                        }
+                        c[q] = make_uint4(w[0], w[1], w[2], w[3]);
+                    }
+                }
+            }
+#pragma unroll
+            for (uint32_t q = 0; q < TSG_U; ++q) {
+                if (hi[q] <= lo[q]) continue;
+                uint8_t* t = reinterpret_cast<uint8_t*>(dst[q]);
+                if (lo[q] == 0u && hi[q] == 16u) {
+                    *reinterpret_cast<uint4*>(t) = c[q];
+                } else {
+                    for (uint32_t i = lo[q]; i < hi[q]; ++i) t[i] = (uint8_t)(word_of(c[q], i >> 2) >> (8u * (i & 3u)));
+                }
+                // byte i of the unit is the segment's payload byte 16 u - o + i: an odd o swaps the pairing
+                const uint32_t s = masked_chunk_sum<true>(c[q], 0u, lo[q], hi[q], od16[q] ? SEL_ODD : SEL_EVEN);
+                accA += inb[q] ? 0u : s;
+                accB += inb[q] ? s : 0u;
+            }
+        }
+        const uint32_t payA = (uint32_t)__builtin_amdgcn_readlane((int)group_sum<64>(accA), 63);
+        const uint32_t payB = (uint32_t)__builtin_amdgcn_readlane((int)group_sum<64>(accB), 63);
+
+        // the headers: the template's words with the segment's own fields
+        if (lane < nw) {
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+                if (b == 1 && !hasB) break;
+                const uint32_t k = b ? kB : kA, pl = b ? plB : plA;
+                const uint32_t seq = seq0 + (uint32_t)((uint64_t)k * per);
+                const uint32_t tlen = bswap16(thl + pl);                             // the pseudo header's length word
+                const uint32_t tcrc = finalize(csum + tlen + bswap16(seq >> 16) + bswap16(seq & 0xFFFFu) + (b ? payB : payA));
+                uint32_t v = tw;
+                if (v6) {
+                    v = lane == 1u ? (v & 0xFFFF0000u) | tlen : v;                   // payload length
+                } else {
+                    const uint32_t len = bswap16(H + pl), id = bswap16((id0 + k) & 0xFFFFu);
+                    const uint32_t ncrc = finalize(nsum + len + id + 0x0040u);       // frag = 40 00
+                    v = lane == 0u ? (v & 0xFFFFu) | (len << 16) : v;
+                    v = lane == 1u ? id | (0x0040u << 16) : v;
+                    v = lane == 2u ? (v & 0xFFFFu) | (bswap16(ncrc) << 16) : v;
+                }
+                v = j == 1u ? __builtin_bswap32(seq) : v;
+                v = j == 4u ? (v & 0xFFFF0000u) | bswap16(tcrc) : v;
+                uint8_t* t = reinterpret_cast<uint8_t*>(b ? dB : dA) + 4u * lane;
+                if ((reinterpret_cast<uint64_t>(t) & 3u) == 0u) {
+                    *reinterpret_cast<uint32_t*>(t) = v;
+                } else {
+                    t[0] = (uint8_t)v;
+                    t[1] = (uint8_t)(v >> 8);
+                    t[2] = (uint8_t)(v >> 16);
+                    t[3] = (uint8_t)(v >> 24);
+                }
+            }
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int pico_csum_launch_tcp_segment(const void* base, uint64_t base_len, const void* strm, uint32_t n_stream,
+                                 const uint32_t* groups, uint32_t n_seg, void* out, uint64_t out_len, const void* out_desc,
+                                 uint32_t stride, void* o_seg, uint32_t* o_count, uint8_t* verdict, void* stream) {
+    if (n_stream == 0) return (int)hipSuccess;
+    TcpSegArgs a{static_cast<const uint8_t*>(base), base_len, static_cast<const pico_csum_desc_dev*>(strm), n_stream,
+                 groups, n_seg, stride, static_cast<uint8_t*>(out), out_len,
+                 static_cast<const pico_csum_desc_dev*>(out_desc), static_cast<pico_csum_desc_dev*>(o_seg), o_count,
+                 verdict};
+    if (n_stream >= TCPSEG_SHORT_MIN && (uint64_t)n_seg <= (uint64_t)TCPSEG_SHORT_SEGS * n_stream)
+        hipLaunchKernelGGL((tcp_segment_kernel<1u, TCPSEG_SHORT_U>), dim3(n_stream), dim3(64), 0,
+                           static_cast<hipStream_t>(stream), a);
+    else
+        hipLaunchKernelGGL((tcp_segment_kernel<4u, 3u>), dim3(n_stream), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    return (int)hipGetLastError();
+}
+
+}  // extern "C"

@@ -496,3 +496,70 @@ def ipv4_oversized(lengths, mtu: int = 1500, stride: int = 1504, seed: int = 31,
         ooff[g] = pos
         pos += int(cap[g])
     return buf, off, dlen.astype(np.uint32), groups, ooff, cap, int(reserved.sum()), pos + 16
+
+
+def tcpseg_count(payload: int, per: int) -> int:
+    """Segments pico_tcp_segment_batch_dev emits for `payload` bytes at `per` bytes a segment:
+    max(1, ceil(payload / per)) -- no payload is one bare-header frame."""
+    return max(1, -(-payload // per))
+
+
+def tcp_streams(lengths, family=4, thl=20, per=1448, stride: int = 1504, seed: int = 51, align=0, out_off: int = 12,
+                spare: int = 0, seq=None, ident=None):
+    """Send units for pico_tcp_segment_batch_dev: per stream a network header (family 4: IPv4, IHL 5;
+    6: IPv6, no extension header), a TCP header of `thl` bytes (PSH|ACK, options arbitrary) and
+    `lengths[g]` payload bytes, contiguous; the fields the batch does not read (IPv4 len / frag /
+    crc, IPv6 payload length, TCP crc) are arbitrary.  family, thl, per, align (the header's address
+    mod 16 in the buffer), seq and ident (template seq / IPv4 id; random when None): one value or one
+    per stream.  Output regions are laid out back to back, each starting at out_off mod 16 and
+    holding exactly the segments at `stride`; every group reserves its segment count + `spare` slots.
+    Returns (buffer, stream offsets uint64, stream bytes uint32, per uint32[n], groups uint32[n, 2] =
+    (first slot, slots reserved), out offsets uint64, out capacities uint32, n_seg, out_len)."""
+    lengths = np.asarray(lengths, dtype=np.int64)
+    n = lengths.size
+    fam = np.broadcast_to(np.asarray(family, dtype=np.uint32), (n,))
+    thls = np.broadcast_to(np.asarray(thl, dtype=np.uint32), (n,))
+    pers = np.broadcast_to(np.asarray(per, dtype=np.uint32), (n,)).copy()
+    aligns = np.broadcast_to(np.asarray(align, dtype=np.uint32), (n,))
+    rng = np.random.default_rng(seed)
+    seqs = rng.integers(0, 1 << 32, n, dtype=np.uint64) if seq is None else np.broadcast_to(np.asarray(seq, np.uint64), (n,))
+    ids = rng.integers(0, 1 << 16, n, dtype=np.uint32) if ident is None else np.broadcast_to(np.asarray(ident, np.uint32), (n,))
+    off = np.zeros(n, np.uint64)
+    hl = np.zeros(n, np.int64)
+    pos = 0
+    pieces = []
+    for g, L in enumerate(lengths.tolist()):
+        tl = int(thls[g])
+        if int(fam[g]) == 6:
+            h = rng.integers(0, 256, 40, dtype=np.uint8)
+            h[0], h[6], h[7] = 0x60 | (int(h[0]) & 15), 6, 64
+        else:
+            h = rng.integers(0, 256, 20, dtype=np.uint8)
+            h[0], h[8], h[9] = 0x45, 64, 6
+            h[4], h[5] = int(ids[g]) >> 8, int(ids[g]) & 0xFF
+            h[12:16] = [10, int(rng.integers(256)), int(rng.integers(256)), 1]
+            h[16:20] = [192, 168, int(rng.integers(256)), 2]
+        t = rng.integers(0, 256, tl, dtype=np.uint8)
+        t[4:8] = [(int(seqs[g]) >> s) & 0xFF for s in (24, 16, 8, 0)]
+        t[12], t[13] = (tl // 4) << 4, 0x18
+        pos += (int(aligns[g]) - pos) % 16
+        off[g] = pos
+        hl[g] = h.size + tl
+        pieces.append(np.concatenate([h, t, random_bytes(seed * 1000003 + g, L)]))
+        pos += pieces[-1].size
+    buf = random_bytes(seed ^ 0x7C95, pos + 16)
+    for g in range(n):
+        buf[int(off[g]):int(off[g]) + pieces[g].size] = pieces[g]
+    cnt = np.array([tcpseg_count(int(L), int(p)) for L, p in zip(lengths.tolist(), pers.tolist())], np.int64)
+    reserved = (cnt + spare).astype(np.uint32)
+    first = np.concatenate([[0], np.cumsum(reserved[:-1])]).astype(np.uint32)
+    groups = np.stack([first, reserved], axis=1).astype(np.uint32)
+    last = hl + lengths - (cnt - 1) * pers.astype(np.int64)
+    cap = ((cnt - 1) * stride + last).astype(np.uint32)
+    ooff = np.zeros(n, np.uint64)
+    pos = 0
+    for g in range(n):
+        pos += (out_off - pos) % 16
+        ooff[g] = pos
+        pos += int(cap[g])
+    return buf, off, (hl + lengths).astype(np.uint32), pers, groups, ooff, cap, int(reserved.sum()), pos + 16
