@@ -54,7 +54,9 @@ extern "C" {
  *      carried state (pico_ipv4_pre_forward_checks in full);
  *   4: pico_csum_release_thread_scratch; the reassembly's flat-grid scratch is freed at thread exit;
  *   4 (added, no bump): pico_ipv4_fragment_batch_dev -- a new entry point breaks no caller;
- *   4 (added, no bump): pico_tcp_segment_batch_dev -- likewise. */
+ *   4 (added, no bump): pico_tcp_segment_batch_dev -- likewise;
+ *   4 (added, no bump): pico_tcp_coalesce_batch_dev and its three verdict values, which no other batch
+ *      returns -- likewise. */
 #define PICO_CSUM_ABI_VERSION 4
 
 /* picoTCP pico_err values used here (include/pico_protocol.h:27,31,38 + ENODEV) */
@@ -103,7 +105,9 @@ struct pico_csum_desc {
  *   NAT:                   ACCEPT, MALFORMED, FRAG, UNTOUCHED
  *   reassembly:            ACCEPT, L4_BAD, MALFORMED
  *   fragmentation (TX):    ACCEPT, MALFORMED
- *   TCP segmentation (TX): ACCEPT, MALFORMED */
+ *   TCP segmentation (TX): ACCEPT, MALFORMED
+ *   TCP coalescing (RX):   per connection ACCEPT, MALFORMED; per segment ACCEPT, NET_BAD (IPv4), L4_BAD,
+ *                          MALFORMED, FRAG, TCP_CTRL, TCP_OLD, TCP_HELD */
 #define PICO_CSUM_V_ACCEPT    1u  /* delivered to the transport and every checksum the reference
                                      checks passes: hand the frame on (a stack built with CRC=0
                                      need not check it again) */
@@ -133,6 +137,16 @@ struct pico_csum_desc {
 #define PICO_CSUM_V_UNTOUCHED 32u /* NAT batch only (same bit as V_DROP_L2): left as it is -- no
                                      rewrite record (the host's tuple lookup failed), or a protocol
                                      the reference's NAT returns -1 on (pico_nat.c:472-474, :537-539) */
+
+#define PICO_CSUM_V_TCP_CTRL  32u /* TCP coalescing batch only (same bit as V_DROP_L2): a segment for the host's
+                                     state machine -- flags other than ACK or PSH|ACK (SYN, FIN, RST, none:
+                                     tcp_action_by_flags, pico_tcp.c:2787-2815) or no payload
+                                     (segment_from_frame returns NULL, :101); header verified, NO transport check */
+#define PICO_CSUM_V_TCP_OLD   64u /* TCP coalescing batch only (same bit as V_ARP): not on the chain, seq before
+                                     its end -- a duplicate, a retransmission or an overlap, which the reference
+                                     drops (pico_tcp.c:1687); payload not read */
+#define PICO_CSUM_V_TCP_HELD 128u /* TCP coalescing batch only (same bit as V_IPV6): not on the chain, seq at or
+                                     beyond its end -- not delivered in this call; payload not read */
 
 /* ---------------------------------------------------------------- layer 1 */
 
@@ -481,6 +495,74 @@ int pico_tcp_segment_batch_dev(const void *d_base, uint64_t base_len, const stru
                                uint64_t out_len, const struct pico_csum_desc *d_out_desc, uint32_t seg_stride,
                                struct pico_csum_desc *d_out_seg, uint32_t *d_out_count, uint8_t *d_verdict,
                                uint32_t flags, void *stream);
+
+/* TCP receive coalescing (what a NIC calls LRO / GRO): each connection's received segments are verified
+ * and the in-order byte stream is delivered into one contiguous region, in one pass that reads each
+ * delivered payload byte once.  The inverse of pico_tcp_segment_batch_dev -- its d_out / d_out_seg go
+ * in as they are -- and the batch form of pico_transport_crc_check (stack/pico_socket.c:1916-1968) +
+ * tcp_data_in (modules/pico_tcp.c:1717-1776, with segment_from_frame's copy, :97-119) +
+ * pico_tcp_read (:1149-1182, a second copy): three passes over every received byte in the reference.
+ *   d_seg[]    one received frame each: desc.off -> the network header, desc.len = bytes available from
+ *              there (nothing past it or past base_len is read, with the whole-16-byte-block read rule
+ *              above), desc.seed = 0.  The version nibble selects the family: IPv4 (any IHL >= 5, proto
+ *              6) or IPv6 with nxthdr 6 and no extension header.
+ *   d_groups[] 2 uint32 per connection: first segment, count, IN ARRIVAL ORDER (the host has matched the
+ *              4-tuple: the socket lookup is control plane, as NAT's tuple table is)
+ *   d_conn[]   2 uint32 per connection: rcv_nxt, cflags.  cflags bit 0 = the connection's sack_ok; the
+ *              other bits are reserved and must be 0.
+ *   d_out_desc[] per connection: output region in d_out (off any alignment -- off = 0 mod 16: whole-line
+ *              stores; len = capacity, which acts as the receive window)
+ *   flags      reserved: anything but 0 is -EINVAL
+ * Per segment, its FIRST outcome in the reference's order (d_seg_verdict[i], written for every segment
+ * of every group that lies inside n_seg):
+ *   1. MALFORMED  the frame past base_len, a header past desc.len, an infeasible IPv4 length, a version
+ *                 other than 4 / 6, proto / nxthdr != 6, IPv6 40 + payload length > desc.len, a transport
+ *                 shorter than 20 bytes, thl < 20 or thl > the transport length (tcp_data_in, :1735);
+ *      NET_BAD    the IPv4 header checksum;  MALFORMED again: an invalid source, the evil bit, IHL < 5;
+ *      FRAG       MF or an offset: route the frame to the reassembly.
+ *      These are pico_ipv4_checksum_batch_dev's RX rules, in its order.
+ *   2. TCP_CTRL   flags other than ACK or PSH|ACK, or a zero-length payload: for the host's state
+ *                 machine.  The segment is not part of the chain: it is treated as if it had not arrived.
+ *   3. The chain, among the remaining candidates: cur = rcv_nxt; repeatedly take the EARLIEST ARRIVAL with
+ *      seq == cur that has not been struck, cur += payload_len (mod 2^32).  With sack_ok the search is
+ *      over the whole group (the reference queues a segment ahead of rcv_nxt, tcp_data_in_high_segment,
+ *      :1693-1714, and scrolls over it later, :1677-1683; a second arrival of a queued seq is refused
+ *      by pico_tree_insert, :201).  Without, a segment counts only if it arrives AFTER the previously
+ *      taken one (the reference drops a high segment, :1696): the search starts behind the last taken
+ *      index.  A member whose bytes do not fit in the remaining capacity ends the chain.  A member is
+ *      copied to out + (seq - rcv_nxt) and its TCP checksum is verified from the bytes copied: IPv4
+ *      with pico_tcp_checksum_ipv4's pseudo header; IPv6 ALWAYS with the TCP pseudo header
+ *      (pico_tcp_checksum_ipv6) -- what PICO_CSUM_F_NXTHDR_DISPATCH selects in the RX batch; the
+ *      reference's byte-9 dispatch quirk is deliberately not followed here: a coalesced stream must not
+ *      depend on an address byte.  Every member that fails is STRUCK (L4_BAD, for good) and the chain is
+ *      planned again without the struck ones, until a planned chain verifies in full: a later
+ *      retransmission of that seq may take a struck member's place.  That is what the reference does in
+ *      arrival order, since a bad segment never reaches the socket.
+ *   4. With the chain's end E final: its members ACCEPT; a candidate not on it (and not struck) with seq
+ *      before E (pico_seq_compare) TCP_OLD; one at or beyond E TCP_HELD -- not delivered in this call,
+ *      its payload not read, so its checksum not judged: the host resubmits held segments with the next
+ *      burst if the connection has SACK, and forgets them otherwise.
+ *   d_out_len[g]  E - rcv_nxt: the host's new rcv_nxt is rcv_nxt + out_len
+ *   d_verdict[g]  ACCEPT (out_len 0 included), or MALFORMED = nothing of the region is written, out_len 0,
+ *              every segment of the group MALFORMED (where the group lies inside n_seg): an empty group or
+ *              one past n_seg, more than 512 segments, a region past out_len, reserved cflags.
+ * Bytes [0, out_len) of the region are the stream; region bytes past out_len are unspecified (a struck
+ * member, or a member of a chain planned before a strike, may have been copied there); no byte outside
+ * the region is written.  d_out_len, d_seg_verdict and d_verdict may each be NULL.  Regions and groups
+ * of different connections must not overlap.
+ * One documented difference: pico_tcp_read walks the tree by overlap (:1164-1171), so with a queued
+ * segment that partly overlaps the chain it reads past rcv_nxt, out of that segment's tail; the batch
+ * delivers up to rcv_nxt, what the stack has ACKed.  For segments cut from one consistent byte stream
+ * the first out_len bytes agree.  No queue limit (PICO_DEFAULT_SOCKETQ) is enforced: the capacity is
+ * the window.  The host keeps the TCP state: ACKs, tcp_ack, FIN / RST, SACK
+ * blocks.  One launch, one workgroup per connection (four waves; one wave in batches of 3072
+ * connections or more with at most 16 segments a connection on average), no library scratch; results
+ * never depend on the launch shape. */
+int pico_tcp_coalesce_batch_dev(const void *d_base, uint64_t base_len, const struct pico_csum_desc *d_seg,
+                                uint32_t n_seg, const uint32_t *d_groups, const uint32_t *d_conn, uint32_t n_conn,
+                                void *d_out, uint64_t out_len, const struct pico_csum_desc *d_out_desc,
+                                uint32_t *d_out_len, uint8_t *d_seg_verdict, uint8_t *d_verdict, uint32_t flags,
+                                void *stream);
 
 /* ---------------------------------------------------------------- layer 3 */
 

@@ -34,6 +34,7 @@ EXPORTED = (
     "pico_ipv6_reassemble_batch_dev",
     "pico_ipv4_fragment_batch_dev",
     "pico_tcp_segment_batch_dev",
+    "pico_tcp_coalesce_batch_dev",
     "pico_csum_ctx_create",
     "pico_csum_ctx_destroy",
     "pico_checksum_batch_uniform_host",
@@ -62,6 +63,7 @@ ABI_VERSION = 4
 V_DROP_L2, V_ARP, V_IPV6 = 32, 64, 128
 V_UNTOUCHED = 32            # NAT batch (same bit as V_DROP_L2)
 V_LOCAL_SRC, V_DUPLICATE = 32, 64   # forwarding batch (same bits as V_DROP_L2 / V_ARP)
+V_TCP_CTRL, V_TCP_OLD, V_TCP_HELD = 32, 64, 128   # TCP coalescing batch (same bits as V_DROP_L2 / V_ARP / V_IPV6)
 EINVAL, ENODEV, EIO, ENOMEM = 22, 19, 5, 12
 
 
@@ -109,6 +111,7 @@ def load() -> ctypes.CDLL:
     sig("pico_ipv6_reassemble_batch_dev", ctypes.c_int, vp, u64, vp, u32, vp, u32, vp, u64, vp, vp, vp, vp, u32, vp)
     sig("pico_ipv4_fragment_batch_dev", ctypes.c_int, vp, u64, vp, u32, u32, vp, u32, vp, u64, vp, u32, vp, vp, vp, vp, u32, vp)
     sig("pico_tcp_segment_batch_dev", ctypes.c_int, vp, u64, vp, u32, vp, u32, vp, u64, vp, u32, vp, vp, vp, u32, vp)
+    sig("pico_tcp_coalesce_batch_dev", ctypes.c_int, vp, u64, vp, u32, vp, vp, u32, vp, u64, vp, vp, vp, vp, u32, vp)
     sig("pico_csum_ctx_create", vp, ctypes.c_int, u64)
     sig("pico_csum_ctx_destroy", None, vp)
     sig("pico_checksum_batch_uniform_host", ctypes.c_int, vp, vp, u64, u32, u32, u32, vp)

@@ -26,7 +26,8 @@ import torch
 
 from . import _lib
 from ._lib import (F_NXTHDR_DISPATCH, F_TX, F_WRITE, V_ACCEPT, V_ARP, V_DROP_L2, V_DUPLICATE,  # noqa: F401
-                   V_EXPIRED, V_FRAG, V_IPV6, V_L4_BAD, V_LOCAL_SRC, V_MALFORMED, V_NET_BAD, V_UNTOUCHED)
+                   V_EXPIRED, V_FRAG, V_IPV6, V_L4_BAD, V_LOCAL_SRC, V_MALFORMED, V_NET_BAD, V_TCP_CTRL, V_TCP_HELD,
+                   V_TCP_OLD, V_UNTOUCHED)
 
 DESC_DTYPE = np.dtype([("off", "<u8"), ("len", "<u4"), ("seed", "<u4")])
 # struct pico_csum_nat (include/pico_csum.h): the NAT batch's per-datagram record
@@ -405,6 +406,50 @@ def tcp_segment_batch(base: torch.Tensor, stream_desc: torch.Tensor, groups: tor
                                               _ptr(out), out.numel(), _ptr(out_desc), seg_stride, _ptr(out_seg),
                                               _ptr(cnt), _ptr(v), flags, _stream_handle(stream)))
     return v, cnt
+
+
+def tcp_coalesce_batch(base: torch.Tensor, seg_desc: torch.Tensor, n_seg: int, groups: torch.Tensor,
+                       conn: torch.Tensor, out: torch.Tensor, out_desc: torch.Tensor, flags: int = 0, stream=None,
+                       results=None):
+    """TCP receive coalescing: every received segment verified and each connection's in-order byte
+    stream delivered into one contiguous region in the same pass (pico_transport_crc_check,
+    pico_socket.c:1916-1968; tcp_data_in, pico_tcp.c:1717-1776; pico_tcp_read, :1149-1182): the
+    inverse of tcp_segment_batch, whose `out` / `out_seg` go in as `base` / `seg_desc`.  seg_desc = one
+    received frame per descriptor (off -> IPv4 or IPv6 header, len = bytes available); groups = uint32
+    (first segment, count) pairs per connection in arrival order, conn = uint32 (rcv_nxt, cflags) pairs
+    (bit 0: sack_ok), both int32 tensors of 2*n; out = uint8 device buffer, out_desc[g] = the
+    connection's region (off, capacity = the window).  flags: reserved, 0.  Returns (verdict uint8[n],
+    out_len int32[n], seg_verdict uint8[n_seg]): V_ACCEPT / V_MALFORMED per connection, the stream
+    bytes delivered (the new rcv_nxt is rcv_nxt + out_len), and per segment V_ACCEPT, V_NET_BAD,
+    V_L4_BAD, V_MALFORMED, V_FRAG, V_TCP_CTRL, V_TCP_OLD or V_TCP_HELD; `results` may pass that triple
+    preallocated, any of them None to skip it."""
+    for t, nm in ((base, "base"), (seg_desc, "seg_desc"), (groups, "groups"), (conn, "conn"), (out, "out"),
+                  (out_desc, "out_desc")):
+        _require_device(t, nm)
+        if t.device != base.device:
+            raise ValueError(f"{nm} is on {t.device}, the batch on {base.device}")
+    _require_u8(base, "base")
+    _require_u8(out, "out")
+    n = groups.numel() // 2
+    for t, nm in ((groups, "groups"), (conn, "conn")):
+        if t.element_size() != 4 or not t.is_contiguous() or t.numel() < 2 * n:
+            raise ValueError(f"{nm} must be a contiguous 32-bit tensor of one pair per connection")
+    if seg_desc.numel() * seg_desc.element_size() < 16 * n_seg or out_desc.numel() * out_desc.element_size() < 16 * n:
+        raise ValueError("descriptor tensor shorter than its count")
+    dev = base.device
+    if results is None:
+        results = (torch.empty(n, dtype=torch.uint8, device=dev), torch.empty(n, dtype=torch.int32, device=dev),
+                   torch.empty(n_seg, dtype=torch.uint8, device=dev))
+    v, ol, sv = results
+    for t, nm, cnt, sz in ((v, "verdict", n, 1), (ol, "out_len", n, 4), (sv, "seg_verdict", n_seg, 1)):
+        if t is not None:
+            _check_out(t, cnt, nm, dev, sz)
+    lib = _lib.load()
+    _lib.check("pico_tcp_coalesce_batch_dev",
+               lib.pico_tcp_coalesce_batch_dev(_ptr(base), base.numel(), _ptr(seg_desc), n_seg, _ptr(groups), _ptr(conn), n,
+                                               _ptr(out), out.numel(), _ptr(out_desc), _ptr(ol), _ptr(sv), _ptr(v), flags,
+                                               _stream_handle(stream)))
+    return v, ol, sv
 
 
 STREAM_OFF = 0xFF

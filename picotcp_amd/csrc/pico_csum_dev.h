@@ -1,6 +1,6 @@
 // pico_csum_dev.h -- device helpers shared by the gfx950 kernel TUs of libpicocsum
 // (pico_csum_k_raw.hip, pico_csum_k_sorted.hip, pico_csum_k_frag.hip, pico_csum_k_fragtx.hip,
-// pico_csum_k_tcpseg.hip).
+// pico_csum_k_tcpseg.hip, pico_csum_k_tcprx.hip).
 // Header-only, internal; everything lives in an anonymous namespace (one copy per TU).
 //
 // The kernels of picoTCP's Internet checksum.
@@ -302,6 +302,68 @@ __device__ __forceinline__ uint32_t masked_chunk_sum(const uint4 v, uint32_t ch,
     return dot2_add(d, dot2_add(c, dot2_add(b, dot2_add(a, 0u))));
 }
 
+constexpr uint32_t NONE = 0xFFFFFFFFu;
+
+// ---------------------------------------------------------------- IPv4 header rules
+//
+// pico_ipv4_process_in (pico_ipv4.c:381-456) on the header's five words, avail >= 20 bytes at the
+// header: IHL / total length (uint16 wrap, :395) / max_allowed (:386); the header and pseudo-header
+// sums; after the header check (finish_frame): pico_ipv4_is_valid_src (:425-428, :187-229 --
+// 255.255.255.255, 224-254.x.x.x, 127/8 from a device that is not "loop"), the evil bit
+// (:431-435), IHL < 5 (:438-443): PV_DROP; MF or an offset (:446-455): PV_FRAG, handed to
+// reassembly -- then only the header is summed.  The transport dispatch: RX TCP and UDP (a UDP crc
+// field past the frame: PV_DROP); TX TCP and ICMP, or with nat (F_NAT: pico_nat.c:443-449,
+// :461-465, :511-517, :527-532) TCP and UDP recomputed in full, ICMP only its header checksum --
+// a TX transport shorter than its header: MALFORMED.  xoff: the crc field in the transport (NONE:
+// no field is read).  hl / tl / proto / ipcrc are set whatever the length checks say (they go
+// into fin).
+struct Ip4 {
+    uint32_t hl, tl, proto, ipcrc, pseudo, hdr20, post, verdict, xoff;
+    bool parsed, l4_needed;
+};
+[[maybe_unused]] __device__ __forceinline__ Ip4 ipv4_classify(const uint32_t (&H)[5], uint32_t avail, bool tx,
+                                                              bool nat) {
+    Ip4 c{};
+    c.verdict = V_MALFORMED;
+    c.xoff = NONE;
+    const uint32_t ihl = H[0] & 0x0Fu;
+    c.hl = 20u + (ihl > 5u ? 4u * (ihl - 5u) : 0u);
+    const uint32_t tot = (((H[0] >> 16) & 0xFFu) << 8) | (H[0] >> 24);
+    c.proto = (H[2] >> 8) & 0xFFu;
+    c.ipcrc = H[2] >> 16;
+    c.tl = (tot - c.hl) & 0xFFFFu;
+    const uint32_t max_allowed = (avail - 20u) & 0xFFFFu;
+    if (c.hl > avail || (!tx && c.tl > max_allowed) || c.hl + c.tl > avail) return c;
+    c.parsed = true;
+    c.verdict = 0;
+#pragma unroll
+    for (int m = 0; m < 5; ++m) c.hdr20 = dot2_add(H[m], c.hdr20);
+    c.pseudo = (H[3] & 0xFFFFu) + (H[3] >> 16) + (H[4] & 0xFFFFu) + (H[4] >> 16) + (c.proto << 8) +
+               (((c.tl & 0xFFu) << 8) | (c.tl >> 8));
+    const uint32_t frag = ((H[1] >> 8) & 0xFF00u) | (H[1] >> 24);
+    const uint32_t s0 = H[3] & 0xFFu;
+    const bool bad_src = H[3] == 0xFFFFFFFFu || (s0 != 0xFFu && (s0 & 0xE0u) == 0xE0u) || s0 == 0x7Fu;
+    if (!tx && (bad_src || (frag & 0x8000u) || ihl < 5u)) c.post = PV_DROP;
+    else if (frag & 0x3FFFu) c.post = PV_FRAG;
+    if (c.post) return c;
+    if (!tx) {
+        if (c.proto == 6u) {
+            c.l4_needed = true;
+        } else if (c.proto == 17u) {
+            if (c.hl + 8u > avail) c.post = PV_DROP;
+            else { c.l4_needed = true; c.xoff = 6u; }
+        }
+    } else {
+        const uint32_t need = c.proto == 6u ? 20u : 8u;
+        const uint32_t x = c.proto == 6u ? 16u : c.proto == 17u && nat ? 6u : c.proto == 1u && !nat ? 2u : NONE;
+        if (x != NONE) {
+            if (c.tl < need) c.verdict |= V_MALFORMED;
+            else { c.l4_needed = true; c.xoff = x; }
+        }
+    }
+    return c;
+}
+
 // ---------------------------------------------------------------- IPv6 extension headers
 //
 // pico_ipv6_extension_headers (modules/pico_ipv6.c:707-809) with the sequence check before it
@@ -464,8 +526,6 @@ struct FlatArgs {
     uint32_t mac_lo;      // ETH: the device's MAC as stored (bytes 0-3, 4-5), with F_MACF
     uint32_t mac_hi;
 };
-
-constexpr uint32_t NONE = 0xFFFFFFFFu;
 
 
 // ---------------------------------------------------------------- dispatch

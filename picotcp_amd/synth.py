@@ -563,3 +563,119 @@ def tcp_streams(lengths, family=4, thl=20, per=1448, stride: int = 1504, seed: i
         ooff[g] = pos
         pos += int(cap[g])
     return buf, off, (hl + lengths).astype(np.uint32), pers, groups, ooff, cap, int(reserved.sum()), pos + 16
+
+
+def tcp_rx_frame(rng, seq: int, payload, family: int = 4, thl: int = 20, flags: int = 0x18, ihl: int = 5) -> np.ndarray:
+    """One received TCP frame as the wire delivers it, every checksum valid: an IPv4 header of
+    4 * ihl bytes (DF, options arbitrary) or a 40-byte IPv6 header (no extension header), a TCP
+    header of `thl` bytes (seq, flags; ports, ack, window and options from rng) and the payload."""
+    payload = np.asarray(payload, dtype=np.uint8)
+    tl = thl + payload.size
+    t = rng.integers(0, 256, thl, dtype=np.uint8)
+    t[4:8] = [(seq >> s) & 0xFF for s in (24, 16, 8, 0)]
+    t[12], t[13], t[16], t[17] = (thl // 4) << 4, flags, 0, 0
+    if family == 6:
+        h = rng.integers(0, 256, 40, dtype=np.uint8)
+        h[0], h[4], h[5], h[6], h[7] = 0x60 | (int(h[0]) & 15), tl >> 8, tl & 0xFF, 6, 64
+        ph = np.concatenate([h[8:40], np.array([0, 0, tl >> 8, tl & 0xFF, 0, 0, 0, 6], np.uint8)])
+    else:
+        h = rng.integers(0, 256, 4 * ihl, dtype=np.uint8)
+        tot = 4 * ihl + tl
+        h[0], h[2], h[3], h[6], h[7], h[8], h[9], h[10], h[11] = 0x40 | ihl, tot >> 8, tot & 0xFF, 0x40, 0, 64, 6, 0, 0
+        h[12:16] = [10, int(rng.integers(256)), int(rng.integers(256)), 1]
+        h[16:20] = [192, 168, int(rng.integers(256)), 2]
+        c = _finalize(_ones_sum(h))
+        h[10], h[11] = c >> 8, c & 0xFF
+        ph = np.concatenate([h[12:20], np.array([0, 6, tl >> 8, tl & 0xFF], np.uint8)])
+    c = _finalize(_ones_sum(np.concatenate([t, payload]), _ones_sum(ph)))
+    t[16], t[17] = c >> 8, c & 0xFF
+    return np.concatenate([h, t, payload])
+
+
+def tcp_rx_pack(conns, align=0, out_off: int = 0, seed: int = 81, slack=0):
+    """The arrays of pico_tcp_coalesce_batch_dev for `conns`, a list of (frames, rcv_nxt, sack_ok,
+    capacity) with frames in arrival order: the frames laid out one after another, frame i at `align`
+    mod 16 (one value or one per frame, in batch order) with desc.len = its size + `slack` (one value
+    or one per frame; negative: the descriptor ends inside the frame), output regions back to back,
+    each at out_off mod 16.  Returns (buffer, seg offsets uint64, seg bytes uint32, groups uint32[n, 2]
+    = (first, count), conn uint32[n, 2] = (rcv_nxt, cflags), out offsets uint64, out capacities
+    uint32, out_len)."""
+    frames = [f for c in conns for f in c[0]]
+    m = len(frames)
+    aligns = np.broadcast_to(np.asarray(align, dtype=np.int64), (m,))
+    slacks = np.broadcast_to(np.asarray(slack, dtype=np.int64), (m,))
+    off, ln = np.zeros(m, np.uint64), np.zeros(m, np.uint32)
+    pos = 0
+    for i, f in enumerate(frames):
+        pos += (int(aligns[i]) - pos) % 16
+        off[i] = pos
+        ln[i] = f.size + int(slacks[i])
+        pos += f.size + max(int(slacks[i]), 0)
+    buf = random_bytes(seed ^ 0x3B1D, pos)
+    for i, f in enumerate(frames):
+        buf[int(off[i]):int(off[i]) + f.size] = f
+    cnt = np.array([len(c[0]) for c in conns], np.uint32)
+    first = np.concatenate([[0], np.cumsum(cnt[:-1])]).astype(np.uint32)
+    groups = np.stack([first, cnt], axis=1).astype(np.uint32)
+    conn = np.array([[c[1] & 0xFFFFFFFF, 1 if c[2] else 0] for c in conns], np.uint32).reshape(-1, 2)
+    cap = np.array([c[3] for c in conns], np.uint32)
+    ooff = np.zeros(len(conns), np.uint64)
+    pos = 0
+    for g in range(len(conns)):
+        pos += (out_off - pos) % 16
+        ooff[g] = pos
+        pos += int(cap[g])
+    return buf, off, ln, groups, conn, ooff, cap, pos + 16
+
+
+def tcp_rx_bursts(n_conn: int, seed: int = 83, family=4, thl=32, per=1448, max_bytes: int = 12000, corrupt: bool = True):
+    """Received-segment groups for pico_tcp_coalesce_batch_dev, each cut from one byte stream (the send
+    segmentation's split: `per` payload bytes a segment): per connection an in-order run disturbed by
+    swaps, exact duplicates, a retransmission of a byte range with another split, a hole (a segment
+    lost: every later one is ahead of rcv_nxt) and, with `corrupt`, a flipped payload bit followed
+    later by a good copy and a flipped IPv4 header bit.  family, thl, per: one value or one per
+    connection.  Returns (conns for tcp_rx_pack with capacity = the stream's bytes, streams): streams[g]
+    = the connection's whole byte stream, whose byte 0 has seq rcv_nxt."""
+    rng = np.random.default_rng(seed)
+    fam = np.broadcast_to(np.asarray(family), (n_conn,))
+    thls = np.broadcast_to(np.asarray(thl), (n_conn,))
+    pers = np.broadcast_to(np.asarray(per), (n_conn,))
+    conns, streams = [], []
+    for g in range(n_conn):
+        f, t, p = int(fam[g]), int(thls[g]), int(pers[g])
+        P = int(rng.integers(1, max_bytes // 2))
+        data = random_bytes(seed * 1000003 + g, P)
+        rcv = int(rng.integers(0, 1 << 32)) if g % 5 else (1 << 32) - int(rng.integers(1, P + 1))
+        mk = lambda a, b: tcp_rx_frame(rng, (rcv + a) & 0xFFFFFFFF, data[a:b], f, t, 0x18 if (a // p) % 2 else 0x10)
+        cuts = [(a, min(a + p, P)) for a in range(0, P, p)]
+        frames = [mk(a, b) for a, b in cuts]
+        for _ in range(int(rng.integers(0, 3))):                     # swaps
+            if len(frames) > 1:
+                i = int(rng.integers(0, len(frames) - 1))
+                frames[i], frames[i + 1] = frames[i + 1], frames[i]
+        for _ in range(int(rng.integers(0, 3))):                     # exact duplicates
+            i = int(rng.integers(0, len(frames)))
+            frames.insert(int(rng.integers(i, len(frames) + 1)), frames[i].copy())
+        if P > 3 and rng.integers(2):                                # a retransmission with another split
+            a = int(rng.integers(0, P - 2))
+            b = int(rng.integers(a + 1, P + 1))
+            q = max(1, (b - a) // int(rng.integers(1, 4)))
+            at = int(rng.integers(0, len(frames) + 1))
+            for k, x in enumerate(range(a, b, q)):
+                frames.insert(at + k, mk(x, min(x + q, b)))
+        if len(cuts) > 2 and rng.integers(3) == 0:                   # a hole: the first copy of a segment is lost
+            frames.pop(int(rng.integers(1, len(frames))))
+        if corrupt and rng.integers(2):                              # a flipped payload bit, a good copy later
+            i = int(rng.integers(0, len(frames)))
+            bad = frames[i].copy()
+            bad[-1 - int(rng.integers(0, min(8, bad.size - (40 if f == 6 else 20) - t)))] ^= 1 << int(rng.integers(8))
+            good = frames[i]
+            frames[i] = bad
+            frames.insert(int(rng.integers(i + 1, len(frames) + 1)), good)
+        if corrupt and f == 4 and rng.integers(2):                   # a flipped IPv4 header bit
+            i = int(rng.integers(0, len(frames)))
+            frames[i] = frames[i].copy()
+            frames[i][8] ^= 0x10                                     # (the TTL: only the header checksum sees it)
+        conns.append((frames, rcv, bool(rng.integers(2)), P))
+        streams.append(data)
+    return conns, streams

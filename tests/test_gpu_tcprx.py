@@ -1,0 +1,481 @@
+"""GPU: TCP receive coalescing (pico_tcp_coalesce_batch_dev) against the numpy restatement of its
+contract (tests/tcprx_ref.py, pinned to the compiled reference stack by tests/test_ref_tcprx.py) and
+against that stack's own deliveries (tests/golden/ref_tcprx_cases.npz).  Every comparison is over the WHOLE output buffer, pre-filled with a
+canary: bytes [0, out_len) of every region and every byte outside the regions are compared exactly;
+an ACCEPT connection's region bytes past out_len are excluded (the contract leaves them unspecified)
+and nothing else is.  The launcher has two launch shapes: four waves per connection (every test but
+one) and one wave per connection (test_large_batch_one_wave_per_connection)."""
+from __future__ import annotations
+
+import numpy as np
+import pytest
+import torch
+
+from picotcp_amd import batch, synth
+from tests import tcprx_ref as R
+from tests import test_ref_tcprx as RF
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+CANARY = 0xA5
+A, NB, LB, MF, FR, CT, OL, HE = (R.V_ACCEPT, R.V_NET_BAD, R.V_L4_BAD, R.V_MALFORMED, R.V_FRAG, R.V_TCP_CTRL, R.V_TCP_OLD,
+                                 R.V_TCP_HELD)
+
+
+def to_dev(a: np.ndarray) -> torch.Tensor:
+    return torch.from_numpy(np.array(a, copy=True, order="C")).to(DEV)      # (a copy: the fixture's arrays are read-only)
+
+
+def pairs_dev(a: np.ndarray) -> torch.Tensor:
+    return to_dev(np.ascontiguousarray(a, np.uint32).reshape(-1).view(np.int32))
+
+
+def dev_args(buf, sd, groups, conn, od):
+    return (to_dev(buf), to_dev(sd.view(np.uint8)) if sd.size else torch.zeros(16, dtype=torch.uint8, device=DEV),
+            sd.size, pairs_dev(groups), pairs_dev(conn)), to_dev(od.view(np.uint8))
+
+
+def check_arrays(buf, sd, groups, conn, out_size, od):
+    """GPU == restatement on every result and on every specified byte of the output buffer."""
+    want_out = np.full(out_size, CANARY, np.uint8)
+    wv, wl, ws = R.coalesce(buf, sd, groups, conn, want_out, od)
+    out = torch.full((out_size,), CANARY, dtype=torch.uint8, device=DEV)
+    args, d_od = dev_args(buf, sd, groups, conn, od)
+    sv0 = torch.zeros(max(sd.size, 1), dtype=torch.uint8, device=DEV)
+    res = (torch.empty(len(wv), dtype=torch.uint8, device=DEV), torch.empty(len(wv), dtype=torch.int32, device=DEV), sv0)
+    v, ol, sv = batch.tcp_coalesce_batch(*args, out, d_od, results=res)
+    torch.cuda.synchronize()
+    np.testing.assert_array_equal(v.cpu().numpy(), wv)
+    np.testing.assert_array_equal(ol.cpu().numpy().view(np.uint32), wl)
+    np.testing.assert_array_equal(sv.cpu().numpy()[:sd.size], ws)
+    got = out.cpu().numpy()
+    keep = ~R.region_tail_mask(out_size, od, wv, wl)
+    bad = np.flatnonzero((got != want_out) & keep)
+    assert bad.size == 0, f"{bad.size} bytes differ, first at {bad[:8].tolist()}"
+    return wv, wl, ws, got
+
+
+def check(conns, **kw):
+    buf, off, ln, groups, conn, ooff, cap, out_size = synth.tcp_rx_pack(conns, **kw)
+    sd, od = batch.make_desc(off, ln), batch.make_desc(ooff, cap)
+    return check_arrays(buf, sd, groups, conn, out_size, od) + (od,)
+
+
+def cut(rng, rcv, data, bounds, family=4, thl=20, **kw):
+    """Frames of data[a:b] for (a, b) in bounds, seq = rcv + a."""
+    return [synth.tcp_rx_frame(rng, (rcv + a) & 0xFFFFFFFF, data[a:b], family, thl, **kw) for a, b in bounds]
+
+
+def even(P, per):
+    return [(a, min(a + per, P)) for a in range(0, P, per)]
+
+
+def stream_of(got, od, g, n):
+    o = int(od["off"][g])
+    return got[o:o + n]
+
+
+@pytest.mark.parametrize("out_off", [0, 5])
+def test_reference_fixture(out_off):
+    """The 24 bursts the compiled reference stack received: the kernel delivers what the stack
+    acknowledged (rcv_nxt after) and what pico_socket_read returned, byte for byte, and agrees with the
+    restatement on every verdict."""
+    a = RF.fixture()
+    buf, sd, groups, conn, od, out_size = RF.batch_of(a, out_off=out_off)
+    wv, wl, ws, got = check_arrays(buf, sd, groups, conn, out_size, od)
+    RF.check_against_reference(a, wv, wl, ws, got, od)
+    net, l4 = RF.corrupted(a)
+    assert (ws[net] == NB).all() and (ws[l4] == LB).sum() >= 6
+
+
+# ---------------------------------------------------------------- lengths and alignments
+
+@pytest.mark.parametrize("out_off", [0, 1, 7, 12, 15])
+def test_edge_lengths_and_alignments(out_off):
+    """Payloads of 1, 15, 16, 17, 31, 33, 1447 and 1448 bytes -- each connection two segments of that
+    length, so the second one's place starts mid-line -- x every source alignment 0..15 x thl 20 / 32 /
+    60 x IPv4 IHL 5 / IHL 6 / IPv6, for output regions at out_off mod 16."""
+    rng = np.random.default_rng(100 + out_off)
+    conns, aligns = [], []
+    for li, pl in enumerate((1, 15, 16, 17, 31, 33, 1447, 1448)):
+        for a in range(16):
+            for ti, thl in enumerate((20, 32, 60)):
+                fam, ihl = ((4, 5), (4, 6), (6, 5))[(a + li + ti) % 3]
+                data = synth.random_bytes(1000 * li + 16 * a + ti, 2 * pl)
+                rcv = int(rng.integers(0, 1 << 32))
+                conns.append((cut(rng, rcv, data, [(0, pl), (pl, 2 * pl)], fam, thl, ihl=ihl), rcv, bool(a & 1), 2 * pl))
+                aligns += [a, (a + 5) % 16]
+    wv, wl, ws, got, od = check(conns, align=aligns, out_off=out_off)
+    assert (wv == A).all() and (ws == A).all()
+    np.testing.assert_array_equal(wl, [c[3] for c in conns])
+
+
+# ---------------------------------------------------------------- arrival orders
+
+@pytest.mark.parametrize("family", [4, 6])
+def test_arrival_orders_with_and_without_sack(family):
+    """In order, reversed and shuffled, each with and without sack_ok: with SACK the whole stream is
+    delivered whatever the order; without, only what arrives behind the previously taken segment."""
+    rng = np.random.default_rng(110 + family)
+    P, per = 9 * 700 + 123, 700
+    data = synth.random_bytes(111, P)
+    rcv = 0x12345678
+    frames = cut(rng, rcv, data, even(P, per), family, 32)
+    shuf = list(rng.permutation(len(frames)))
+    conns = []
+    for order in (list(range(10)), list(range(9, -1, -1)), shuf):
+        for sack in (True, False):
+            conns.append(([frames[i] for i in order], rcv, sack, P))
+    wv, wl, ws, got, od = check(conns, align=np.arange(60) % 16, out_off=3)
+    assert wl[0] == wl[1] == wl[2] == wl[4] == P and wl[3] == 700          # reversed, no SACK: only segment 0 (the last arrival)
+    np.testing.assert_array_equal(ws[30:40], [HE] * 9 + [A])
+    for g in (0, 1, 2, 4):
+        np.testing.assert_array_equal(stream_of(got, od, g, P), data)
+    # the shuffle without SACK: exactly the greedy in-arrival-order walk
+    cur, n = 0, 0
+    for i in shuf:
+        if i == cur:
+            cur, n = cur + 1, n + min(per, P - per * i)
+    assert wl[5] == n
+
+
+def test_duplicates_overlaps_and_old():
+    """Exact duplicates (the earliest arrival is taken, the later is OLD), a resegmented retransmission
+    that overlaps the chain (OLD), one that bridges onto the chain from another split, and groups that
+    are old altogether (out_len 0, ACCEPT)."""
+    rng = np.random.default_rng(120)
+    P = 5000
+    data = synth.random_bytes(121, P)
+    rcv = 0xFFFFF000                                          # the stream crosses 2^32
+    f = cut(rng, rcv, data, even(P, 1000))
+    dup = [f[0], f[1], f[1].copy(), f[0].copy(), f[2], f[3], f[4], f[2].copy()]
+    reseg = cut(rng, rcv, data, [(500, 1500), (1500, 2600)])
+    bridge = cut(rng, rcv, data, [(0, 700), (700, 2000)]) + f[2:]
+    conns = [(dup, rcv, True, P), (dup, rcv, False, P),
+             ([f[0], reseg[0], f[1], reseg[1], f[2], f[3], f[4]], rcv, True, P),
+             (bridge, rcv, False, P),
+             (f[:3], (rcv + 3000) & 0xFFFFFFFF, True, P), (f[:3], (rcv + 3000) & 0xFFFFFFFF, False, P),
+             ([f[1], f[0]], (rcv + 2000) & 0xFFFFFFFF, True, 100)]
+    wv, wl, ws, got, od = check(conns, align=7, out_off=9)
+    np.testing.assert_array_equal(wl, [P, P, P, P, 0, 0, 0])
+    assert (wv == A).all()
+    np.testing.assert_array_equal(ws[:8], [A, A, OL, OL, A, A, A, OL])
+    np.testing.assert_array_equal(ws[16:23], [A, OL, A, OL, A, A, A])
+    np.testing.assert_array_equal(ws[28:36], [OL] * 8)
+    for g in range(4):
+        np.testing.assert_array_equal(stream_of(got, od, g, P), data)
+
+
+def test_hole_holds_what_lies_behind_it():
+    rng = np.random.default_rng(130)
+    P = 6000
+    data = synth.random_bytes(131, P)
+    f = cut(rng, 77, data, even(P, 1000), 6, 20)
+    conns = [(f[:2] + f[3:], 77, True, P), (f[:2] + f[3:], 77, False, P), (f[1:], 77, True, P)]
+    wv, wl, ws, got, od = check(conns, align=2)
+    np.testing.assert_array_equal(wl, [2000, 2000, 0])
+    np.testing.assert_array_equal(ws, [A, A, HE, HE, HE] * 2 + [HE] * 5)
+
+
+def test_rcv_nxt_near_the_wrap():
+    """rcv_nxt = 2^32 - 1, 2^32 - 1448 and 0xFFFFFFFF - 3000 with shuffled arrivals: seq arithmetic mod
+    2^32, OLD / HELD by pico_seq_compare across the wrap."""
+    rng = np.random.default_rng(140)
+    P = 7000
+    data = synth.random_bytes(141, P)
+    conns = []
+    for rcv in (0xFFFFFFFF, (1 << 32) - 1448, 0xFFFFFFFF - 3000):
+        f = cut(rng, rcv, data, even(P, 1448), 4, 32)
+        old = synth.tcp_rx_frame(rng, (rcv - 500) & 0xFFFFFFFF, data[:400])
+        conns.append(([f[2], old, f[0], f[1], f[4]], rcv, True, P))
+    wv, wl, ws, got, od = check(conns, align=11, out_off=5)
+    np.testing.assert_array_equal(wl, [3 * 1448] * 3)
+    np.testing.assert_array_equal(ws, [A, OL, A, A, HE] * 3)
+
+
+# ---------------------------------------------------------------- corruption
+
+def flip(frame, at=-1):
+    b = frame.copy()
+    b[at] ^= 0x04
+    return b
+
+
+@pytest.mark.parametrize("sack", [True, False])
+def test_corrupted_chain_members(sack):
+    """A corrupted chain member first / middle / last in the chain, with a later good copy (it takes
+    the struck one's place) and without (the chain ends there and what lies behind is HELD); several
+    struck in one group; a corrupted segment that is not on the chain is not judged."""
+    rng = np.random.default_rng(150)
+    P = 5 * 900
+    data = synth.random_bytes(151, P)
+    for fam in (4, 6):
+        f = cut(rng, 1000, data, even(P, 900), fam, 32)
+        conns = []
+        for k in (0, 2, 4):
+            bad = f[:k] + [flip(f[k])] + f[k + 1:]
+            conns.append((bad + [f[k]], 1000, sack, P))          # a good copy arrives last
+            conns.append((bad, 1000, sack, P))
+        conns.append(([flip(f[0], -3), flip(f[1], 70)] + f[2:] + [f[1], flip(f[0]), f[0]], 1000, sack, P))
+        conns.append((f[:2] + [f[1].copy(), flip(f[4])], 1000, sack, P))  # the flipped one is beyond the chain's end
+        wv, wl, ws, got, od = check(conns, align=np.arange(64)[:sum(len(c[0]) for c in conns)] % 16, out_off=1)
+        assert (wv == A).all()
+        # with SACK the good copy completes the stream; without, only what arrives behind it counts
+        np.testing.assert_array_equal(wl[:6], [P, 0, P, 1800, P, 3600] if sack else [900, 0, 2700, 1800, P, 3600])
+        np.testing.assert_array_equal(ws[:6], [LB, A, A, A, A, A] if sack else [LB, HE, HE, HE, HE, A])
+        np.testing.assert_array_equal(ws[6:11], [LB, HE, HE, HE, HE])
+        assert wl[6] == (P if sack else 900) and list(ws[33:41]) == ([LB, LB, A, A, A, A, LB, A] if sack else [LB, LB, HE, HE, HE, HE, LB, A])
+        assert wl[7] == 1800 and list(ws[41:45]) == [A, A, OL, HE]
+
+
+def test_header_outcomes():
+    """A corrupted IPv4 header (NET_BAD), a FIN|ACK with data (CTRL: the chain stops there), a pure ACK
+    in the middle of the group (CTRL, the chain goes on), a fragment (FRAG), SYN / RST / no flags, proto
+    17, IPv6 nxthdr 17, thl 16, thl past the transport, version 5, the evil bit, IHL 4: each segment's
+    verdict beside accepted neighbours."""
+    rng = np.random.default_rng(160)
+    P = 4000
+    data = synth.random_bytes(161, P)
+    f = cut(rng, 5, data, even(P, 1000))
+    f6 = cut(rng, 5, data, even(P, 1000), 6, 24)
+
+    def hdr(frame, edits, fix=True):
+        b = frame.copy()
+        for k, val in edits:
+            b[k] = val
+        if fix and (int(b[0]) >> 4) == 4:
+            b[10] = b[11] = 0
+            c = synth._finalize(synth._ones_sum(b[:max(20, 4 * (int(b[0]) & 15))]))     # (IHL < 5: the check covers 20 bytes)
+            b[10], b[11] = c >> 8, c & 0xFF
+        return b
+
+    netbad = hdr(f[1], [(8, 63)], fix=False)
+    finack = synth.tcp_rx_frame(rng, 5 + 1000, data[1000:2000], flags=0x11)
+    ack = synth.tcp_rx_frame(rng, 5 + 1000, data[:0], flags=0x10)
+    frag = hdr(f[1], [(6, 0x20)])
+    conns = [([f[0], netbad, f[2]], 5, True, P), ([f[0], netbad, f[1], f[2]], 5, True, P),
+             ([f[0], finack, f[2], f[3]], 5, True, P), ([f[0], ack, f[1], f[2]], 5, False, P),
+             ([f[0], frag, f[1]], 5, True, P),
+             ([f[0]] + [synth.tcp_rx_frame(rng, 1005, data[1000:2000], flags=x) for x in (0x02, 0x14, 0x00, 0x38)] + [f[1]], 5, False, P),
+             ([f[0], hdr(f[1], [(9, 17)]), hdr(f6[1], [(6, 17)]), hdr(f[1], [(32, 0x40)]), hdr(f6[1], [(52, 0xF0), (4, 0), (5, 40)]),
+               hdr(f[1], [(0, 0x55)]), hdr(f[1], [(6, 0xC0)]), hdr(f[1], [(0, 0x44)]), f6[1]], 5, True, P)]
+    wv, wl, ws, got, od = check(conns, align=4, out_off=12)
+    np.testing.assert_array_equal(wl, [1000, 3000, 1000, 3000, 2000, 2000, 2000])
+    assert list(ws[:7]) == [A, NB, HE, A, NB, A, A] and list(ws[7:11]) == [A, CT, HE, HE] and list(ws[11:15]) == [A, CT, A, A]
+    assert list(ws[15:18]) == [A, FR, A] and list(ws[18:24]) == [A, CT, CT, CT, CT, A]
+    assert list(ws[24:]) == [A, MF, MF, MF, MF, MF, MF, MF, A]
+
+
+# ---------------------------------------------------------------- group sizes, capacity, bounds
+
+@pytest.mark.parametrize("sack", [True, False])
+def test_group_sizes(sack):
+    """1, 64, 65, 128, 129 and 512 segments a connection (shuffled with SACK, in order without: the
+    planner's 64-segment rounds), and 513 (MALFORMED: nothing written, every segment MALFORMED)."""
+    rng = np.random.default_rng(170)
+    conns, want = [], []
+    for k, n in enumerate((1, 64, 65, 128, 129, 512, 513)):
+        per = 37 if n < 512 else 5
+        data = synth.random_bytes(171 + k, n * per - 3)
+        f = cut(rng, 9000 * k, data, even(data.size, per), 4 + 2 * (k & 1), 20)
+        if sack:
+            f = [f[i] for i in rng.permutation(n)]
+        conns.append((f, 9000 * k, sack, data.size))
+        want.append(data)
+    wv, wl, ws, got, od = check(conns, align=np.arange(sum(len(c[0]) for c in conns)) % 16, out_off=6)
+    np.testing.assert_array_equal(wv, [A] * 6 + [MF])
+    np.testing.assert_array_equal(wl, [d.size for d in want[:6]] + [0])
+    assert (ws[:-513] == A).all() and (ws[-513:] == MF).all()
+    for g in range(6):
+        np.testing.assert_array_equal(stream_of(got, od, g, want[g].size), want[g])
+
+
+def test_capacity_is_the_window():
+    """A capacity one byte short of the chain and one short of the last member only: that member is
+    HELD and the rest is delivered; capacity 0; a capacity that ends inside the first member."""
+    rng = np.random.default_rng(180)
+    P = 4 * 1448
+    data = synth.random_bytes(181, P)
+    f = cut(rng, 42, data, even(P, 1448), 4, 32)
+    conns = [(f, 42, True, P - 1), (f, 42, False, 3 * 1448 + 1), (f, 42, True, P), (f, 42, True, 0), (f, 42, True, 1447),
+             ([f[1], f[0], f[3], f[2]], 42, True, P - 1)]
+    wv, wl, ws, got, od = check(conns, align=13, out_off=15)
+    np.testing.assert_array_equal(wl, [3 * 1448, 3 * 1448, P, 0, 0, 3 * 1448])
+    np.testing.assert_array_equal(ws, [A, A, A, HE] * 2 + [A] * 4 + [HE] * 8 + [A, A, HE, A])
+
+
+def test_malformed_segments_and_connections():
+    """A segment whose header or payload runs past desc.len or base_len, and every MALFORMED cause of
+    a connection (an empty group, a group past n_seg, a region past out_len, reserved cflags) beside
+    accepted neighbours: not one byte of a MALFORMED connection's region changes."""
+    rng = np.random.default_rng(190)
+    P = 3000
+    data = synth.random_bytes(191, P)
+    f = cut(rng, 1, data, even(P, 1000), 4, 20)
+    f6 = cut(rng, 1, data, even(P, 1000), 6, 20)
+    conns = [(f, 1, True, P)] * 7 + [(f6, 1, True, P), (f + [f6[0]], 1, True, P)]
+    n = sum(len(c[0]) for c in conns)
+    slack = np.zeros(n, np.int64)
+    slack[1] = -1                                      # conn 0: segment 1's payload one byte past desc.len
+    slack[3] = -985                                    # conn 1: segment 0's descriptor ends inside the TCP header
+    slack[6] = -1010                                   # conn 2: ... inside the IPv4 header
+    slack[22] = -1                                     # conn 7 (IPv6): payload past desc.len
+    slack[23] = -1021                                  # ... the descriptor ends inside the IPv6 header
+    buf, off, ln, groups, conn, ooff, cap, out_size = synth.tcp_rx_pack(conns, align=5, out_off=2, slack=slack)
+    buf = buf[:buf.size - 1]                           # the last segment (an IPv6 one) runs 1 byte past base_len
+    sd, od = batch.make_desc(off, ln), batch.make_desc(ooff, cap)
+    groups, conn, od = groups.copy(), conn.copy(), od.copy()
+    groups[3, 1] = 0                                   # 3: an empty group
+    groups[4, 0] = n - 2                               # 4: a group past n_seg
+    od["off"][5] = out_size - 100                      # 5: a region past out_len
+    conn[6, 1] = 3                                     # 6: reserved cflags
+    wv, wl, ws, got = check_arrays(buf, sd, groups, conn, out_size, od)
+    np.testing.assert_array_equal(wv, [A, A, A, MF, MF, MF, MF, A, A])
+    np.testing.assert_array_equal(wl, [1000, 0, 0, 0, 0, 0, 0, 1000, 3000])
+    assert list(ws[:9]) == [A, MF, HE, MF, HE, HE, MF, HE, HE]
+    assert list(ws[9:15]) == [0] * 6                   # (no group covers them: not written)
+    assert list(ws[15:21]) == [MF] * 6 and list(ws[21:24]) == [A, MF, MF] and list(ws[24:]) == [A, A, A, MF]
+
+
+def test_null_outputs_and_empty_batch():
+    conns, _ = synth.tcp_rx_bursts(6, seed=200, family=[4, 6] * 3)
+    buf, off, ln, groups, conn, ooff, cap, out_size = synth.tcp_rx_pack(conns, align=1)
+    sd, od = batch.make_desc(off, ln), batch.make_desc(ooff, cap)
+    wv, wl, ws, want_out = check_arrays(buf, sd, groups, conn, out_size, od)
+    keep = ~R.region_tail_mask(out_size, od, wv, wl)
+    args, d_od = dev_args(buf, sd, groups, conn, od)
+    for skip in (0, 1, 2, 3):                          # 3: all three outputs NULL
+        out = torch.full((out_size,), CANARY, dtype=torch.uint8, device=DEV)
+        res = [torch.full((k,), 77, dtype=dt, device=DEV) for k, dt in ((6, torch.uint8), (6, torch.int32), (sd.size, torch.uint8))]
+        if skip < 3:
+            res[skip] = None
+        else:
+            res = [None, None, None]
+        v, ol, sv = batch.tcp_coalesce_batch(*args, out, d_od, results=tuple(res))
+        torch.cuda.synchronize()
+        np.testing.assert_array_equal(out.cpu().numpy()[keep], want_out[keep])
+        for t, w in ((v, wv), (ol, wl.view(np.int32)), (sv, ws)):
+            if t is not None:
+                np.testing.assert_array_equal(t.cpu().numpy(), w)
+    out = torch.full((64,), CANARY, dtype=torch.uint8, device=DEV)
+    empty = torch.zeros(0, dtype=torch.int32, device=DEV)
+    v, ol, sv = batch.tcp_coalesce_batch(args[0], torch.zeros(0, dtype=torch.uint8, device=DEV), 0, empty, empty, out,
+                                         torch.zeros(0, dtype=torch.uint8, device=DEV))
+    torch.cuda.synchronize()
+    assert v.numel() == 0 and (out.cpu().numpy() == CANARY).all()
+
+
+def test_graph_replay():
+    """One call captured into a graph and replayed twice: the eager result each time."""
+    conns, _ = synth.tcp_rx_bursts(9, seed=210, family=[4, 6, 4] * 3)
+    buf, off, ln, groups, conn, ooff, cap, out_size = synth.tcp_rx_pack(conns, align=9, out_off=4)
+    sd, od = batch.make_desc(off, ln), batch.make_desc(ooff, cap)
+    wv, wl, ws, want_out = check_arrays(buf, sd, groups, conn, out_size, od)
+    keep = ~R.region_tail_mask(out_size, od, wv, wl)
+    args, d_od = dev_args(buf, sd, groups, conn, od)
+    out = torch.full((out_size,), CANARY, dtype=torch.uint8, device=DEV)
+    res = batch.tcp_coalesce_batch(*args, out, d_od)                        # warm (eager)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        with torch.cuda.graph(g, stream=s):
+            batch.tcp_coalesce_batch(*args, out, d_od, stream=s, results=res)
+    torch.cuda.current_stream().wait_stream(s)
+    for _ in range(2):
+        out.fill_(CANARY)
+        for r in res:
+            r.zero_()
+        g.replay()
+        torch.cuda.synchronize()
+        np.testing.assert_array_equal(out.cpu().numpy()[keep], want_out[keep])
+        np.testing.assert_array_equal(res[0].cpu().numpy(), wv)
+        np.testing.assert_array_equal(res[1].cpu().numpy().view(np.uint32), wl)
+        np.testing.assert_array_equal(res[2].cpu().numpy(), ws)
+
+
+def test_256_connections_in_one_launch():
+    """256 generated bursts (reorder, duplicates, resegmented retransmissions, holes, corruption), both
+    families, header lengths and segment sizes mixed; where nothing was lost or corrupted beyond repair
+    the delivered bytes are the stream's own."""
+    rng = np.random.default_rng(220)
+    n = 256
+    conns, streams = synth.tcp_rx_bursts(n, seed=221, family=rng.choice([4, 6], n), thl=rng.choice([20, 32, 60], n),
+                                         per=rng.choice([536, 1220, 1448], n), max_bytes=8000)
+    m = sum(len(c[0]) for c in conns)
+    wv, wl, ws, got, od = check(conns, align=rng.integers(0, 16, m), out_off=8)
+    assert (wv == A).all() and {A, NB, LB, OL, HE} <= set(ws.tolist())
+    for g in range(n):
+        np.testing.assert_array_equal(stream_of(got, od, g, int(wl[g])), streams[g][:int(wl[g])])
+    assert int((wl == [c[3] for c in conns]).sum()) > n // 4
+
+
+def test_large_batch_one_wave_per_connection():
+    """Batches of 3072 connections or more with at most 16 segments a connection on average run one
+    wave per connection (every other test here: four waves): 3200 generated bursts of small segments,
+    both families, beside one connection of 200 shuffled segments on the one wave -- and the same
+    connections in a batch of 3000 (four waves) give the same results."""
+    rng = np.random.default_rng(240)
+    n = 3200
+    conns, streams = synth.tcp_rx_bursts(n, seed=241, family=rng.choice([4, 6], n), thl=rng.choice([20, 32, 60], n),
+                                         per=rng.choice([64, 100, 257], n), max_bytes=800)
+    data = synth.random_bytes(242, 200 * 9)
+    f = cut(rng, 31, data, even(data.size, 9))
+    conns[7] = ([f[i] for i in rng.permutation(200)], 31, True, data.size)
+    m = sum(len(c[0]) for c in conns)
+    assert m <= 16 * n
+    aligns = rng.integers(0, 16, m)
+    wv, wl, ws, got, od = check(conns, align=aligns, out_off=3)
+    assert (wv == A).all() and wl[7] == data.size and {A, NB, LB, OL, HE} <= set(ws.tolist())
+    np.testing.assert_array_equal(stream_of(got, od, 7, data.size), data)
+    m4 = sum(len(c[0]) for c in conns[:3000])
+    wv4, wl4, ws4, got4, od4 = check(conns[:3000], align=aligns[:m4], out_off=3)
+    np.testing.assert_array_equal(wl4, wl[:3000])
+    np.testing.assert_array_equal(ws4, ws[:m4])
+
+
+# ---------------------------------------------------------------- round trips through the send segmentation
+
+@pytest.mark.parametrize("family", [4, 6])
+def test_round_trip_through_the_send_segmentation(family):
+    """pico_tcp_segment_batch_dev cuts streams (per 1448, an odd per, per 7); its d_out / d_out_seg go
+    in as they are, in order (without SACK) and shuffled within each group (with SACK): the coalesced
+    bytes equal the original payload and out_len == P."""
+    pers = np.array([1448, 1447, 7, 1448, 999, 7])
+    lengths = np.array([64512, 9000, 700, 1, 5000, 64])
+    rcv = np.array([0xFFFFF000, 5, 1 << 31, 0xFFFFFFFF, 77, 0])
+    buf, off, slen, per, groups, ooff, cap, n_seg, out_size = synth.tcp_streams(lengths, family=family, thl=[20, 32, 60, 20, 32, 24],
+                                                                               per=pers, stride=1536, seed=230 + family,
+                                                                               align=np.arange(6) * 3 % 16, seq=rcv)
+    seg_out = torch.zeros(out_size, dtype=torch.uint8, device=DEV)
+    of = torch.zeros(16 * n_seg, dtype=torch.uint8, device=DEV)
+    v, c = batch.tcp_segment_batch(to_dev(buf), to_dev(batch.make_desc(off, slen, per).view(np.uint8)), pairs_dev(groups), n_seg,
+                                   seg_out, to_dev(batch.make_desc(ooff, cap).view(np.uint8)), 1536, out_seg=of)
+    torch.cuda.synchronize()
+    assert (v.cpu().numpy() == A).all()
+    np.testing.assert_array_equal(c.cpu().numpy(), groups[:, 1])
+    H = (20 if family == 4 else 40) + np.array([20, 32, 60, 20, 32, 24])
+    payload = [buf[int(off[g]) + int(H[g]):int(off[g]) + int(slen[g])] for g in range(6)]
+    ro = np.concatenate([[0], np.cumsum(lengths[:-1] + 16)]) + 5
+    od = batch.make_desc(ro, lengths)
+    rsize = int(ro[-1] + lengths[-1] + 16)
+    d_od = to_dev(od.view(np.uint8))
+    rng = np.random.default_rng(231)
+    h_of = of.cpu().numpy().view(R.DESC_DTYPE)
+    for sack in (False, True):
+        segs = h_of.copy()
+        if sack:
+            for a, n in groups:
+                segs[a:a + n] = segs[a:a + n][rng.permutation(int(n))]
+        conn = np.stack([rcv, np.full(6, int(sack))], axis=1).astype(np.uint32)
+        out = torch.full((rsize,), CANARY, dtype=torch.uint8, device=DEV)
+        rv, ol, sv = batch.tcp_coalesce_batch(seg_out, to_dev(segs.view(np.uint8)), n_seg, pairs_dev(groups), pairs_dev(conn), out, d_od)
+        torch.cuda.synchronize()
+        assert (rv.cpu().numpy() == A).all() and (sv.cpu().numpy() == A).all()
+        np.testing.assert_array_equal(ol.cpu().numpy(), lengths)
+        want = np.full(rsize, CANARY, np.uint8)
+        for g in range(6):
+            want[int(ro[g]):int(ro[g]) + int(lengths[g])] = payload[g]
+        np.testing.assert_array_equal(out.cpu().numpy(), want)
