@@ -2,6 +2,10 @@
 // (pico_csum_k_raw.hip, pico_csum_k_sorted.hip, pico_csum_k_frag.hip, pico_csum_k_fragtx.hip,
 // pico_csum_k_tcpseg.hip, pico_csum_k_tcprx.hip).
 // Header-only, internal; everything lives in an anonymous namespace (one copy per TU).
+// In order: the checksum arithmetic and the lane-group sums (every TU); windowed buffer loads
+// (_k_raw, _k_sorted, _k_frag); the IPv4 header rules (_k_sorted, _k_tcprx); the IPv6 extension-header
+// walk (_k_sorted, _k_frag); the 16-byte unit mover, the output-slot rules and the launch-shape
+// thresholds of the scatter / gather batches (_k_fragtx, _k_tcpseg, _k_tcprx); the dispatch shapes.
 //
 // The kernels of picoTCP's Internet checksum.
 //
@@ -509,6 +513,159 @@ __device__ __forceinline__ uint64_t ipv6_walk_packed(const uint8_t* __restrict__
     }
 }
 #undef WBYTE
+
+// ---------------------------------------------------------------- scatter / gather batches (K8-K10)
+//
+// What pico_csum_k_fragtx.hip, pico_csum_k_tcpseg.hip and pico_csum_k_tcprx.hip share: the 16-byte
+// unit mover, the output-slot rules of the two TX batches and the launch-shape thresholds.
+
+__device__ __forceinline__ uint32_t bswap16(uint32_t v) { return ((v & 0xFFu) << 8) | ((v >> 8) & 0xFFu); }
+
+__device__ __forceinline__ uint32_t ld32(const uint8_t* p) {
+    uint32_t w;
+    __builtin_memcpy(&w, p, 4);
+    return w;
+}
+
+__device__ __forceinline__ uint4 load_una(const uint8_t* p) {
+    uint4 v;
+    __builtin_memcpy(&v, p, 16);
+    return v;
+}
+
+__device__ __forceinline__ uint32_t word_of(const uint4& v, uint32_t q) { return sel4(q, v.x, v.y, v.z, v.w); }
+
+// The wave's sum of x, in every lane (an SGPR).
+__device__ __forceinline__ uint32_t wave_total(uint32_t x) {
+    return (uint32_t)__builtin_amdgcn_readlane((int)group_sum<64>(x), 63);
+}
+
+// The 16-byte unit mover: one wave copies the payloads of two members (fragments, segments) A and B
+// -- pl bytes from address s to address d, any alignment each -- and sums them on the way.
+//   * Units lie on the OUTPUT's 16-byte lines: a member whose payload lands o = d & 15 bytes into a
+//     line has units [0, (o + pl + 15) / 16), unit u covering destination bytes d - o + 16 u ... + 15.
+//     The two members' units share one index space, A's first (two 1480-byte payloads fill 3 x 64
+//     lanes); a step takes U rows of 64 units, all loads before the first store.
+//   * The member's bytes are [lo, hi) of a unit's 16: lo = o in unit 0, hi = o + pl - 16 u in the
+//     last one, 0 and 16 elsewhere.  A whole unit is one aligned 16-byte store (NT: non-temporal);
+//     a member's first and last unit get byte stores, so nothing outside [d, d + pl) is written.
+//   * One byte-unaligned 16-byte load per unit, at s - o + 16 u: the source / destination shift
+//     differs from member to member.  Unit 0's load starts up to 15 bytes before the payload; the
+//     callers' payloads lie at least 20 bytes (K8: the IPv4 header) or 40 bytes (K9, K10: network
+//     and TCP header) into their own readable buffer, so that is its byte 5 / 25 or later.
+//   * e = the end of the last 16-byte block that overlaps the member's readable buffer.  The whole-
+//     block read rule of include/pico_csum.h makes [.., e) readable and nothing behind it, so the
+//     one unit whose 16 bytes would run past e is read byte by byte, its [lo, hi) only.
+//   * Every unit's bytes enter a sum (v_dot2).  Byte i of a unit is payload byte 16 u - o + i: for
+//     an odd o the bytes of each 16-bit half are swapped first (SEL_ODD), so the pairing is
+//     relative to the member's own payload start whatever its source address.  SPLIT: A's bytes
+//     into accA, B's into accB; else all into accA, and accB is not touched.
+// hasB false: plB, sB, dB, eB are not used.  All arguments but lane are wave-uniform.
+template <uint32_t U, bool NT, bool SPLIT>
+__device__ __forceinline__ void unit_pair_move(uint64_t sA, uint64_t sB, uint64_t dA, uint64_t dB, uint64_t eA, uint64_t eB,
+                                               uint32_t plA, uint32_t plB, bool hasB, uint32_t lane, uint32_t& accA,
+                                               uint32_t& accB) {
+    const uint32_t oA = (uint32_t)dA & 15u, oB = (uint32_t)dB & 15u;
+    const uint32_t nuA = (oA + plA + 15u) >> 4, nuB = hasB ? (oB + plB + 15u) >> 4 : 0u, nt = nuA + nuB;
+    for (uint32_t x0 = 0; x0 < nt; x0 += 64u * U) {
+        uint4 c[U];
+        uint32_t lo[U], hi[U], od16[U];
+        bool inb[U];
+        uint64_t dst[U];
+#pragma unroll
+        for (uint32_t q = 0; q < U; ++q) {
+            const uint32_t x = x0 + 64u * q + lane;
+            inb[q] = x >= nuA;
+            const uint32_t u = inb[q] ? x - nuA : x, o = inb[q] ? oB : oA, pl = inb[q] ? plB : plA;
+            lo[q] = u == 0u ? o : 0u;
+            hi[q] = x < nt ? (uint32_t)min(16, max((int)(o + pl) - (int)(16u * u), 0)) : 0u;
+            od16[q] = o & 1u;
+            dst[q] = (inb[q] ? dB : dA) + 16u * u - o;                               // 16-byte aligned
+            const uint64_t src = (inb[q] ? sB : sA) + 16u * u - o;
+            const uint64_t e = inb[q] ? eB : eA;
+            c[q] = make_uint4(0, 0, 0, 0);
+            if (hi[q] > lo[q]) {
+                if (src + 16u <= e) {
+                    c[q] = load_una(reinterpret_cast<const uint8_t*>(src));
+                } else {                                                             // the buffer's last unit
+                    uint32_t w[4] = {0, 0, 0, 0};
+                    for (uint32_t i = lo[q]; i < hi[q]; ++i) {
+                        const uint32_t byte = (uint32_t)*reinterpret_cast<const uint8_t*>(src + i) << (8u * (i & 3u));
+                        w[0] |= (i >> 2) == 0u ? byte : 0u;
+                        w[1] |= (i >> 2) == 1u ? byte : 0u;
+                        w[2] |= (i >> 2) == 2u ? byte : 0u;
+                        w[3] |= (i >> 2) == 3u ? byte : 0u;
+                    }
+                    c[q] = make_uint4(w[0], w[1], w[2], w[3]);
+                }
+            }
+        }
+#pragma unroll
+        for (uint32_t q = 0; q < U; ++q) {
+            if (hi[q] <= lo[q]) continue;
+            uint8_t* t = reinterpret_cast<uint8_t*>(dst[q]);
+            if (lo[q] == 0u && hi[q] == 16u) {
+                if constexpr (NT)
+                    __builtin_nontemporal_store((u32x4){c[q].x, c[q].y, c[q].z, c[q].w}, reinterpret_cast<u32x4*>(t));
+                else
+                    *reinterpret_cast<uint4*>(t) = c[q];
+            } else {
+                for (uint32_t i = lo[q]; i < hi[q]; ++i) t[i] = (uint8_t)(word_of(c[q], i >> 2) >> (8u * (i & 3u)));
+            }
+            const uint32_t s = masked_chunk_sum<true>(c[q], 0u, lo[q], hi[q], od16[q] ? SEL_ODD : SEL_EVEN);
+            if constexpr (SPLIT) {
+                accA += inb[q] ? 0u : s;
+                accB += inb[q] ? s : 0u;
+            } else {
+                accA += s;
+            }
+        }
+    }
+}
+
+// The output slots of a TX batch's group (K8, K9): `payload` bytes at `per` a member, members
+// `stride` apart behind `hdr` header bytes each; whole: one member whatever the payload (it must be
+// set for payload 0; per >= 1).  need = the bytes of the output region the group fills.
+struct SlotPlan {
+    uint32_t count, last_pl;
+    uint64_t need;
+};
+
+__device__ __forceinline__ SlotPlan slot_plan(uint32_t payload, uint32_t per, uint32_t stride, uint32_t hdr, bool whole) {
+    SlotPlan s;
+    s.count = whole ? 1u : (payload - 1u) / per + 1u;
+    s.last_pl = (uint32_t)(payload - (uint64_t)(s.count - 1u) * per);
+    s.need = (uint64_t)(s.count - 1u) * stride + hdr + s.last_pl;
+    return s;
+}
+
+// The group's `reserved` slots from slot `first` lie inside the n slots of the batch.
+__device__ __forceinline__ bool slots_in(uint32_t first, uint32_t reserved, uint32_t n) {
+    return first <= n && reserved <= n - first;
+}
+
+// Writes a group's reserved slots (slots_in holds; every thread of the workgroup calls it): the
+// members' descriptors, then {0, 0, 0}; count 0 for a group that fails a check.
+__device__ __forceinline__ void write_slots(pico_csum_desc_dev* slot, uint32_t reserved, uint32_t count, uint64_t off,
+                                            uint32_t stride, uint32_t hdr, uint32_t per, uint32_t last_pl, uint32_t tid,
+                                            uint32_t nthreads) {
+    for (uint32_t k = tid; k < reserved; k += nthreads) {
+        pico_csum_desc_dev f{0, 0, 0};
+        if (k < count) {
+            f.off = off + (uint64_t)k * stride;
+            f.len = hdr + (k + 1u < count ? per : last_pl);
+        }
+        slot[k] = f;
+    }
+}
+
+// Launch shapes: four waves per group; batches of SHORT_GROUPS_MIN groups or more with at most
+// SHORT_SLOTS_AVG members a group on average run one wave per group -- there the per-group latency
+// chain (descriptor, header, first loads, reduction) is what occupancy has to hide.  Measured for
+// K8 (profiles/fragtx/ab_shapes.txt).  K9 and K10 take the pair over as it stands: each compared
+// its two shapes at ONE point, 29360 groups of 7 members (profiles/tcpseg/ab_shapes.txt,
+// profiles/tcprx/ab_shapes.txt), and measured neither threshold.
+constexpr uint32_t SHORT_GROUPS_MIN = 3072u, SHORT_SLOTS_AVG = 16u;
 
 struct FlatArgs {
     uint8_t* base;

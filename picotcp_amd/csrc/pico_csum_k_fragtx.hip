@@ -10,24 +10,16 @@
 // payload); here the pass that scatters the transport reads every byte once anyway, so the
 // whole-datagram transport checksum comes with it.
 //
-// One workgroup per datagram (4 waves; 1 wave in large batches of short datagrams, see the launch
-// shapes below); every check is made before the first store (a MALFORMED datagram writes nothing
-// into its region):
+// One workgroup per datagram; every check is made before the first store (a MALFORMED datagram
+// writes nothing into its region):
 //   1. the 20 template bytes (one lane each): the header's word sum without len / frag / crc and
 //      the pseudo header's address part, once per datagram;
 //   2. wave w takes the fragment pairs w, w + 4, ... (one wave: every pair): fragments 2j and
-//      2j + 1.  Lanes 0..19 write
-//      each fragment's header -- the template with len, frag and the checksum from the template's
-//      sum plus those two words (no re-read).  The payload moves in 16-byte units on the OUTPUT's
-//      16-byte lines (a fragment whose payload starts o bytes into a line has units
-//      [0, (o + payload + 15) / 16)), the two fragments' units in one index space (two 1480-byte
-//      payloads fill 3 x 64 lanes): one byte-unaligned 16-byte load per unit (the source /
-//      destination relative alignment changes from fragment to fragment unless the stride keeps
-//      it), one aligned 16-byte store per whole unit, byte stores for the bytes of a fragment's
-//      first and last unit.  The one unit whose 16 bytes would run past the last 16-byte block
-//      that overlaps the datagram is read byte by byte (the whole-block read rule of
-//      include/pico_csum.h).  Every unit's bytes enter the transport sum on the way (v_dot2; an
-//      odd o swaps the bytes of each 16-bit half first);
+//      2j + 1.  Lanes 0..19 write each fragment's header -- the template with len, frag and the
+//      checksum from the template's sum plus those two words (no re-read).  The two payloads move
+//      and enter the transport sum through the 16-byte unit mover (unit_pair_move, pico_csum_dev.h:
+//      the unit scheme and the read rule are stated there), one sum for the whole datagram -- the
+//      pairing is the datagram's because per is even; the readable block ends with the datagram;
 //   3. the sum is reduced over the workgroup (DPP, then LDS); thread 0 takes the crc field's own
 //      word out of it (the field reads as zero), adds the pseudo header and -- F_WRITE -- stores
 //      the result into the fragment that holds the field, behind the barrier that orders it after
@@ -55,29 +47,10 @@ struct FragTxArgs {
     uint32_t flags;
 };
 
-// Launch shapes (measured: profiles/fragtx/).  Four waves per datagram and three
-// 64-unit slots per step (94 VGPRs); large batches of short datagrams -- FRAGTX_SHORT_MIN datagrams
-// or more, at most FRAGTX_SHORT_FRAGS slots reserved a datagram on average -- one wave per datagram
-// and one slot per step (64 VGPRs, 8 waves a SIMD): there the per-datagram latency chain
-// (descriptor, header, first loads, reduction) is what occupancy has to hide.
-#ifndef FRAGTX_SHORT_MIN
-#define FRAGTX_SHORT_MIN 3072u
-#endif
-#ifndef FRAGTX_SHORT_FRAGS
-#define FRAGTX_SHORT_FRAGS 16u
-#endif
-
-__device__ __forceinline__ uint32_t bswap16(uint32_t v) { return ((v & 0xFFu) << 8) | ((v >> 8) & 0xFFu); }
-
-__device__ __forceinline__ uint4 load_una(const uint8_t* p) {
-    uint4 v;
-    __builtin_memcpy(&v, p, 16);
-    return v;
-}
-
-__device__ __forceinline__ uint32_t word_of(const uint4& v, uint32_t q) { return sel4(q, v.x, v.y, v.z, v.w); }
-
-// FTX_WAVES waves per datagram, FTX_U 64-unit slots per step (3: two 1480-byte payloads)
+// FTX_WAVES waves per datagram, FTX_U 64-unit rows per step.  Launch shapes (measured:
+// profiles/fragtx/): four waves and three rows (two 1480-byte payloads; 94 VGPRs),
+// or -- large batches of short datagrams, SHORT_GROUPS_MIN / SHORT_SLOTS_AVG in pico_csum_dev.h --
+// one wave and one row (64 VGPRs, 8 waves a SIMD).
 template <uint32_t FTX_WAVES, uint32_t FTX_U>
 __global__ __launch_bounds__(64 * FTX_WAVES) void fragment_kernel(FragTxArgs p) {
     __shared__ uint32_t s_acc[FTX_WAVES];
@@ -89,27 +62,18 @@ __global__ __launch_bounds__(64 * FTX_WAVES) void fragment_kernel(FragTxArgs p) 
     const uint32_t per = (p.mtu - 20u) & ~7u;                       // mtu >= 28: per >= 8
 
     // ---- checks (workgroup-uniform): nothing is stored for a datagram that fails one
-    const bool slots_in = first <= p.n_frag && reserved <= p.n_frag - first;
-    bool bad = d.off > p.base_len || d.len > p.base_len - d.off || d.len < 20u || d.len > 65535u || !slots_in;
+    const bool slots_ok = slots_in(first, reserved, p.n_frag);
+    bool bad = d.off > p.base_len || d.len > p.base_len - d.off || d.len < 20u || d.len > 65535u || !slots_ok;
     const uint32_t tl = bad ? 0u : d.len - 20u;
     const bool whole = d.len <= p.mtu;                              // pico_ipv4.c:1059: frag = DF, one frame
-    const uint32_t count = whole || tl == 0u ? 1u : (tl + per - 1u) / per;
-    const uint32_t last_pl = whole ? tl : tl - (count - 1u) * per;
-    const uint64_t need = (uint64_t)(count - 1u) * p.stride + 20u + last_pl;
-    bad = bad || reserved < count || od.off > p.out_len || od.len > p.out_len - od.off || need > od.len;
+    const SlotPlan sp = slot_plan(tl, per, p.stride, 20u, whole || tl == 0u);
+    const uint32_t count = sp.count, last_pl = sp.last_pl;
+    bad = bad || reserved < count || od.off > p.out_len || od.len > p.out_len - od.off || sp.need > od.len;
     const uint8_t* h = p.base + d.off;
     if (!bad) bad = ((uint32_t)h[0] & 0x0Fu) != 5u;
 
-    if (p.o_frag && slots_in) {                                     // the group's slots: descriptors, then {0, 0, 0}
-        for (uint32_t k = tid; k < reserved; k += 64u * FTX_WAVES) {
-            pico_csum_desc_dev f{0, 0, 0};
-            if (!bad && k < count) {
-                f.off = od.off + (uint64_t)k * p.stride;
-                f.len = 20u + (k + 1u < count ? per : last_pl);
-            }
-            p.o_frag[first + k] = f;
-        }
-    }
+    if (p.o_frag && slots_ok)
+        write_slots(p.o_frag + first, reserved, bad ? 0u : count, od.off, p.stride, 20u, per, last_pl, tid, 64u * FTX_WAVES);
     if (bad) {
         if (tid == 0) {
             if (p.o_count) p.o_count[g] = 0u;
@@ -123,8 +87,8 @@ __global__ __launch_bounds__(64 * FTX_WAVES) void fragment_kernel(FragTxArgs p) 
     const uint32_t hb = lane < 20u ? (uint32_t)h[lane] : 0u;
     const uint32_t hw = lane & 1u ? hb << 8 : hb;                   // the byte's place in its LE word
     const bool tmpl = lane < 20u && !(lane == 2u || lane == 3u || lane == 6u || lane == 7u || lane == 10u || lane == 11u);
-    const uint32_t hsum = (uint32_t)__builtin_amdgcn_readlane((int)group_sum<64>(tmpl ? hw : 0u), 63);
-    const uint32_t asum = (uint32_t)__builtin_amdgcn_readlane((int)group_sum<64>(lane >= 12u && lane < 20u ? hw : 0u), 63);
+    const uint32_t hsum = wave_total(tmpl ? hw : 0u);
+    const uint32_t asum = wave_total(lane >= 12u && lane < 20u ? hw : 0u);
     const uint32_t proto = (uint32_t)__builtin_amdgcn_readlane((int)hb, 9);
 
     // ---- 2. scatter + sum
@@ -138,9 +102,6 @@ __global__ __launch_bounds__(64 * FTX_WAVES) void fragment_kernel(FragTxArgs p) 
         const bool hasB = kB < count;
         const uint32_t plA = kA + 1u < count ? per : last_pl, plB = hasB ? (kB + 1u < count ? per : last_pl) : 0u;
         const uint64_t dA = D + (uint64_t)kA * p.stride, dB = D + (uint64_t)kB * p.stride;
-        const uint32_t oA = (uint32_t)(dA + 20u) & 15u, oB = (uint32_t)(dB + 20u) & 15u;
-        const uint32_t nuA = (oA + plA + 15u) >> 4, nuB = hasB ? (oB + plB + 15u) >> 4 : 0u, nt = nuA + nuB;
-
         // the headers: the template's bytes with len, frag (offset >> 3 | MF; DF on a datagram sent
         // whole) and pico_ipv4_checksum
         if (lane < 20u) {
@@ -158,53 +119,11 @@ __global__ __launch_bounds__(64 * FTX_WAVES) void fragment_kernel(FragTxArgs p) 
             }
         }
 
-        for (uint32_t x0 = 0; x0 < nt; x0 += 64u * FTX_U) {
-            uint4 c[FTX_U];
-            uint32_t lo[FTX_U], hi[FTX_U], od16[FTX_U];
-            uint64_t dst[FTX_U];
-#pragma unroll
-            for (uint32_t q = 0; q < FTX_U; ++q) {
-                const uint32_t x = x0 + 64u * q + lane;
-                const bool inb = x >= nuA;
-                const uint32_t u = inb ? x - nuA : x, o = inb ? oB : oA, pl = inb ? plB : plA, k = inb ? kB : kA;
-                // the unit's fragment bytes are [lo, hi) of its 16
-                lo[q] = u == 0u ? o : 0u;
-                hi[q] = x < nt ? (uint32_t)min(16, max((int)(o + pl) - (int)(16u * u), 0)) : 0u;
-                od16[q] = o & 1u;
-                dst[q] = (inb ? dB : dA) + 20u + 16u * u - o;                        // 16-byte aligned
-                const uint64_t src = S + (uint64_t)k * per + 16u * u - o;            // >= the header's byte 5
-                c[q] = make_uint4(0, 0, 0, 0);
-                if (hi[q] > lo[q]) {
-                    if (src + 16u <= a1) {
-                        c[q] = load_una(reinterpret_cast<const uint8_t*>(src));
-                    } else {                                                         // the datagram's last unit
-                        uint32_t w[4] = {0, 0, 0, 0};
-                        for (uint32_t i = lo[q]; i < hi[q]; ++i) {
-                            const uint32_t byte = (uint32_t)*reinterpret_cast<const uint8_t*>(src + i) << (8u * (i & 3u));
-                            w[0] |= (i >> 2) == 0u ? byte : 0u;
-                            w[1] |= (i >> 2) == 1u ? byte : 0u;
-                            w[2] |= (i >> 2) == 2u ? byte : 0u;
-                            w[3] |= (i >> 2) == 3u ? byte : 0u;
-                        }
-                        c[q] = make_uint4(w[0], w[1], w[2], w[3]);
-                    }
-                }
-            }
-#pragma unroll
-            for (uint32_t q = 0; q < FTX_U; ++q) {
-                if (hi[q] <= lo[q]) continue;
-                uint8_t* t = reinterpret_cast<uint8_t*>(dst[q]);
-                if (lo[q] == 0u && hi[q] == 16u) {
-                    *reinterpret_cast<uint4*>(t) = c[q];      // (cached: non-temporal measured slower here)
-                } else {
-                    for (uint32_t i = lo[q]; i < hi[q]; ++i) t[i] = (uint8_t)(word_of(c[q], i >> 2) >> (8u * (i & 3u)));
-                }
-                // byte i of the unit is transport byte k per + 16 u - o + i: an odd o swaps the pairing
-                acc += masked_chunk_sum<true>(c[q], 0u, lo[q], hi[q], od16[q] ? SEL_ODD : SEL_EVEN);
-            }
-        }
+        const uint64_t sA = S + (uint64_t)kA * per, sB = S + (uint64_t)kB * per;
+        // (cached whole-unit stores: non-temporal measured slower here)
+        unit_pair_move<FTX_U, false, false>(sA, sB, dA + 20u, dB + 20u, a1, a1, plA, plB, hasB, lane, acc, acc);
     }
-    acc = (uint32_t)__builtin_amdgcn_readlane((int)group_sum<64>(acc), 63);
+    acc = wave_total(acc);
     if (lane == 0) s_acc[wv] = acc;
     __syncthreads();        // (also orders the F_WRITE store below after the scatter's stores)
 
@@ -245,7 +164,7 @@ int pico_csum_launch_fragment(const void* base, uint64_t base_len, const void* d
                  groups, n_frag, stride, static_cast<uint8_t*>(out), out_len,
                  static_cast<const pico_csum_desc_dev*>(out_desc), static_cast<pico_csum_desc_dev*>(o_frag), o_count,
                  o_l4, verdict, flags};
-    if (n_dgram >= FRAGTX_SHORT_MIN && (uint64_t)n_frag <= (uint64_t)FRAGTX_SHORT_FRAGS * n_dgram)
+    if (n_dgram >= SHORT_GROUPS_MIN && (uint64_t)n_frag <= (uint64_t)SHORT_SLOTS_AVG * n_dgram)
         hipLaunchKernelGGL((fragment_kernel<1u, 1u>), dim3(n_dgram), dim3(64), 0, static_cast<hipStream_t>(stream), a);
     else
         hipLaunchKernelGGL((fragment_kernel<4u, 3u>), dim3(n_dgram), dim3(256), 0, static_cast<hipStream_t>(stream), a);

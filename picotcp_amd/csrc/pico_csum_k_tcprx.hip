@@ -1,9 +1,9 @@
 // pico_csum_k_tcprx.hip -- TCP receive coalescing (what a NIC calls LRO / GRO): a connection's
 // received segments verified and their in-order byte stream delivered into one contiguous region,
 // in one pass that reads each delivered payload byte once -- and its launcher.  The inverse of the
-// send segmentation (pico_csum_k_tcpseg.hip), whose 16-byte unit scheme and per-segment sums it
-// keeps, and the TCP sibling of the reassembly gather (pico_csum_k_frag.hip).  Helpers, the IPv4
-// header rules (ipv4_classify) and the arithmetic contract: pico_csum_dev.h.  The contract:
+// send segmentation (pico_csum_k_tcpseg.hip), whose per-segment sums it keeps, and the TCP sibling
+// of the reassembly gather (pico_csum_k_frag.hip).  Helpers, the IPv4 header rules (ipv4_classify),
+// the 16-byte unit mover (unit_pair_move) and the arithmetic contract: pico_csum_dev.h.  The contract:
 // include/pico_csum.h, pico_tcp_coalesce_batch_dev.
 //
 // Reference: pico_transport_crc_check (stack/pico_socket.c:1916-1968), pico_tcp_input /
@@ -12,8 +12,7 @@
 // rcv_nxt is queued with SACK and dropped without, :1693-1714; one behind it is dropped, :1687),
 // segment_from_frame (:97-119: a copy of the payload) and pico_tcp_read (:1149-1182: a second copy).
 //
-// One workgroup per connection (4 waves; 1 wave in large batches of short groups, see the launch
-// shapes below):
+// One workgroup per connection:
 //   1. every thread parses segment headers into LDS (seg_parse): the network header's rules, the
 //      IPv4 header checksum on the spot, the TCP flags, seq and payload length, and the word sum of
 //      the pseudo header and the TCP header -- the gather then only adds payload;
@@ -21,13 +20,10 @@
 //      scan per 64 arrivals; then, from cur = its end, a ballot for seq == cur over the candidates, 64
 //      a round, takes the earliest arrival (without SACK: behind the last taken one), until none
 //      matches or the next one does not fit the region;
-//   3. all waves gather the chain's members two at a time, wave w the pairs w, w + 4, ...: units on
-//      the OUTPUT's 16-byte lines (a member whose place starts o bytes into a line has units [0, (o +
-//      payload + 15) / 16)), one byte-unaligned 16-byte load and one aligned non-temporal 16-byte store per whole
-//      unit, byte stores for a member's first and last unit, the one unit whose 16 bytes would run
-//      past the last 16-byte block of the segment's buffer read byte by byte; every unit's bytes enter
-//      its OWN member's sum (v_dot2, an odd o swaps the bytes of each 16-bit half), two accumulators
-//      and two DPP reductions per pair;
+//   3. all waves gather the chain's members two at a time, wave w the pairs w, w + 4, ..., through
+//      unit_pair_move: a member's place in the region follows from its seq alone, whole units are
+//      stored non-temporally, each member's readable block ends with its own segment's buffer, and
+//      every unit's bytes enter its OWN member's sum, two accumulators and two DPP reductions per pair;
 //   4. a member whose sum fails is struck (L4_BAD); if any was, wave 0 plans again without them and
 //      the new chain is gathered IN FULL: a placement depends on seq alone, but between two rounds a
 //      struck chain's later members may have been copied over a place the final chain fills from a
@@ -42,14 +38,10 @@ namespace {
 
 constexpr uint32_t TCPRX_MAX = 512u;        // segments per connection handled on device
 constexpr uint32_t V_TCP_CTRL = 32u, V_TCP_OLD = 64u, V_TCP_HELD = 128u;   // include/pico_csum.h
-// Launch shapes, the send segmentation's two: four waves per connection; large batches of short
-// groups -- TCPRX_SHORT_MIN connections or more, at most TCPRX_SHORT_SEGS segments a connection on
-// average -- one wave per connection: there the per-connection latency chain (descriptors, headers,
-// plan, first loads, reduction) is what occupancy has to hide, and four waves share two to four
-// pairs.  Measured at ONE point, 29360 connections of 7 segments (profiles/tcprx/ab_shapes.txt); the
-// two thresholds are the segmentation kernel's values, taken over as they stand, NOT measured here.
-constexpr uint32_t TCPRX_SHORT_MIN = 3072u;
-constexpr uint32_t TCPRX_SHORT_SEGS = 16u;
+// Launch shapes, the send segmentation's two (the thresholds: SHORT_GROUPS_MIN / SHORT_SLOTS_AVG,
+// pico_csum_dev.h): four waves per connection; large batches of short groups one wave per
+// connection -- there four waves would share two to four pairs.  Measured at ONE point, 29360
+// connections of 7 segments (profiles/tcprx/ab_shapes.txt).
 constexpr uint32_t TRX_U = 3u;              // 64-unit rows per gather step: two 1448-byte payloads
 
 struct TcpRxArgs {
@@ -79,22 +71,6 @@ struct TcpRxLds {
     uint8_t st[TCPRX_MAX];      // 0: a candidate for the chain; else the segment's verdict
     uint32_t nchain, end, anybad;
 };
-
-__device__ __forceinline__ uint32_t ld32(const uint8_t* p) {
-    uint32_t w;
-    __builtin_memcpy(&w, p, 4);
-    return w;
-}
-
-__device__ __forceinline__ uint32_t bswap16(uint32_t v) { return ((v & 0xFFu) << 8) | ((v >> 8) & 0xFFu); }
-
-__device__ __forceinline__ uint4 load_una(const uint8_t* p) {
-    uint4 v;
-    __builtin_memcpy(&v, p, 16);
-    return v;
-}
-
-__device__ __forceinline__ uint32_t word_of(const uint4& v, uint32_t q) { return sel4(q, v.x, v.y, v.z, v.w); }
 
 __device__ __forceinline__ uint32_t uni(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
 __device__ __forceinline__ uint64_t uni64(uint64_t x) { return ((uint64_t)uni((uint32_t)(x >> 32)) << 32) | uni((uint32_t)x); }
@@ -280,61 +256,11 @@ __global__ __launch_bounds__(64 * TRX_WAVES) void tcp_coalesce_kernel(TcpRxArgs 
             const uint64_t eA = (sA + plA + uni(L.trail[iA]) + 15u) & ~(uint64_t)15;
             const uint64_t eB = (sB + uni(L.pl[iB]) + uni(L.trail[iB]) + 15u) & ~(uint64_t)15;
             const uint64_t dA = uni64(D + (uint32_t)(L.seq[iA] - rcv_nxt)), dB = uni64(D + (uint32_t)(L.seq[iB] - rcv_nxt));
-            const uint32_t oA = (uint32_t)dA & 15u, oB = (uint32_t)dB & 15u;
-            const uint32_t nuA = (oA + plA + 15u) >> 4, nuB = hasB ? (oB + plB + 15u) >> 4 : 0u, nt = nuA + nuB;
 
             uint32_t accA = 0, accB = 0;
-            for (uint32_t x0 = 0; x0 < nt; x0 += 64u * TRX_U) {
-                uint4 c[TRX_U];
-                uint32_t lo[TRX_U], hi[TRX_U], od16[TRX_U];
-                bool inb[TRX_U];
-                uint64_t dst[TRX_U];
-#pragma unroll
-                for (uint32_t q = 0; q < TRX_U; ++q) {
-                    const uint32_t x = x0 + 64u * q + lane;
-                    inb[q] = x >= nuA;
-                    const uint32_t u = inb[q] ? x - nuA : x, o = inb[q] ? oB : oA, pl = inb[q] ? plB : plA;
-                    // the unit's member bytes are [lo, hi) of its 16
-                    lo[q] = u == 0u ? o : 0u;
-                    hi[q] = x < nt ? (uint32_t)min(16, max((int)(o + pl) - (int)(16u * u), 0)) : 0u;
-                    od16[q] = o & 1u;
-                    dst[q] = (inb[q] ? dB : dA) + 16u * u - o;                           // 16-byte aligned
-                    const uint64_t src = (inb[q] ? sB : sA) + 16u * u - o;               // >= the frame's byte 25
-                    const uint64_t e = inb[q] ? eB : eA;
-                    c[q] = make_uint4(0, 0, 0, 0);
-                    if (hi[q] > lo[q]) {
-                        if (src + 16u <= e) {
-                            c[q] = load_una(reinterpret_cast<const uint8_t*>(src));
-                        } else {                                                         // the buffer's last unit
-                            uint32_t w[4] = {0, 0, 0, 0};
-                            for (uint32_t i = lo[q]; i < hi[q]; ++i) {
-                                const uint32_t byte = (uint32_t)*reinterpret_cast<const uint8_t*>(src + i) << (8u * (i & 3u));
-                                w[0] |= (i >> 2) == 0u ? byte : 0u;
-                                w[1] |= (i >> 2) == 1u ? byte : 0u;
-                                w[2] |= (i >> 2) == 2u ? byte : 0u;
-                                w[3] |= (i >> 2) == 3u ? byte : 0u;
-                            }
-                            c[q] = make_uint4(w[0], w[1], w[2], w[3]);
-                        }
-                    }
-                }
-#pragma unroll
-                for (uint32_t q = 0; q < TRX_U; ++q) {
-                    if (hi[q] <= lo[q]) continue;
-                    uint8_t* t = reinterpret_cast<uint8_t*>(dst[q]);
-                    if (lo[q] == 0u && hi[q] == 16u) {
-                        __builtin_nontemporal_store((u32x4){c[q].x, c[q].y, c[q].z, c[q].w}, reinterpret_cast<u32x4*>(t));
-                    } else {
-                        for (uint32_t i = lo[q]; i < hi[q]; ++i) t[i] = (uint8_t)(word_of(c[q], i >> 2) >> (8u * (i & 3u)));
-                    }
-                    // byte i of the unit is the member's payload byte 16 u - o + i: an odd o swaps the pairing
-                    const uint32_t s = masked_chunk_sum<true>(c[q], 0u, lo[q], hi[q], od16[q] ? SEL_ODD : SEL_EVEN);
-                    accA += inb[q] ? 0u : s;
-                    accB += inb[q] ? s : 0u;
-                }
-            }
-            const uint32_t payA = (uint32_t)__builtin_amdgcn_readlane((int)group_sum<64>(accA), 63);
-            const uint32_t payB = (uint32_t)__builtin_amdgcn_readlane((int)group_sum<64>(accB), 63);
+            unit_pair_move<TRX_U, true, true>(sA, sB, dA, dB, eA, eB, plA, plB, hasB, lane, accA, accB);
+            const uint32_t payA = wave_total(accA);
+            const uint32_t payB = wave_total(accB);
             // ---- 4. pico_tcp_checksum over what was copied: a member that fails is struck
             if (lane == 0) {
                 if (finalize(L.hsum[iA] + payA) != 0u) {
@@ -380,7 +306,7 @@ int pico_csum_launch_tcp_coalesce(const void* base, uint64_t base_len, const voi
     TcpRxArgs a{static_cast<const uint8_t*>(base), base_len, static_cast<const pico_csum_desc_dev*>(seg), n_seg, groups,
                 conn, n_conn, static_cast<uint8_t*>(out), out_len, static_cast<const pico_csum_desc_dev*>(out_desc),
                 o_len, seg_verdict, verdict};
-    if (n_conn >= TCPRX_SHORT_MIN && (uint64_t)n_seg <= (uint64_t)TCPRX_SHORT_SEGS * n_conn)
+    if (n_conn >= SHORT_GROUPS_MIN && (uint64_t)n_seg <= (uint64_t)SHORT_SLOTS_AVG * n_conn)
         hipLaunchKernelGGL(tcp_coalesce_kernel<1u>, dim3(n_conn), dim3(64), 0, static_cast<hipStream_t>(stream), a);
     else
         hipLaunchKernelGGL(tcp_coalesce_kernel<4u>, dim3(n_conn), dim3(256), 0, static_cast<hipStream_t>(stream), a);

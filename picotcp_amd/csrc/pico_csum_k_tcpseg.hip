@@ -2,7 +2,8 @@
 // long payload per connection scattered into segment-sized frames, every frame with its own IPv4
 // header checksum and TCP checksum, in one pass that reads each payload byte once -- and its
 // launcher.  The TCP sibling of the fragmentation scatter (pico_csum_k_fragtx.hip), whose output
-// conventions and 16-byte unit scheme it keeps.  Helpers and the arithmetic contract: pico_csum_dev.h.
+// conventions it keeps.  Helpers, the 16-byte unit mover both go through (unit_pair_move) and the
+// arithmetic contract: pico_csum_dev.h.
 //
 // Reference: pico_socket_xmit (stack/pico_socket.c:1322-1358) loops pico_socket_xmit_one
 // (:1070-1127: a frame per `space` bytes, memcpy of the payload); pico_tcp_push
@@ -12,24 +13,16 @@
 // id = ipv4_progressive_id++, frag = DF, pico_ipv4_checksum).  The reference touches every payload
 // byte twice (memcpy, pico_tcp_checksum) and every header twice.
 //
-// One workgroup per stream (4 waves; 1 wave in large batches of short streams, see the launch
-// shapes below); every check is made before the first store (a MALFORMED stream writes nothing
-// into its region):
+// One workgroup per stream; every check is made before the first store (a MALFORMED stream writes
+// nothing into its region):
 //   1. the template, one lane per 32-bit word of its H = N + thl bytes (H <= 100: 25 lanes): the
 //      word sums of the IPv4 header without len / id / frag / crc, of the addresses (the pseudo
 //      header's address part) and of the TCP header without seq / crc, once per stream;
 //   2. wave w takes the segment pairs w, w + 4, ... (one wave: every pair): segments 2j and
-//      2j + 1.  The payload moves in 16-byte units on the OUTPUT's 16-byte lines (a segment whose payload starts o bytes into a
-//      line has units [0, (o + payload + 15) / 16)), the two segments' units in one index space
-//      (two 1448-byte payloads fill 3 x 64 lanes): one byte-unaligned 16-byte load per unit (the
-//      source / destination relative alignment changes from segment to segment unless stride - per
-//      keeps it), one aligned 16-byte store per whole unit, byte stores for the bytes of a
-//      segment's first and last unit.  The one unit whose 16 bytes would run past the last 16-byte
-//      block that overlaps the stream is read byte by byte (the whole-block read rule of
-//      include/pico_csum.h).  Every unit's bytes enter its OWN segment's sum on the way (v_dot2; an
-//      odd o swaps the bytes of each 16-bit half first: the pairing is relative to the segment's
-//      payload start, whatever the parity of k per): two accumulators per lane, two wave
-//      reductions (DPP) per pair -- no LDS, no barrier;
+//      2j + 1.  The two payloads move through unit_pair_move, every unit's bytes into its OWN
+//      segment's sum (the pairing is relative to the segment's payload start, whatever the parity
+//      of k per): two accumulators per lane, two wave reductions (DPP) per pair -- no LDS, no
+//      barrier; the readable block ends with the stream;
 //   3. behind the reductions the wave writes both headers once, complete: the template's words
 //      with len, id + k, DF and pico_ipv4_checksum (IPv4) or the payload length (IPv6), seq +
 //      k per, and pico_tcp_checksum = the template's sums + the segment's own len / seq words + its
@@ -55,33 +48,18 @@ struct TcpSegArgs {
     uint8_t* verdict;
 };
 
-// Launch shapes, the fragmentation kernel's two.  Four waves per stream and three
-// 64-unit slots per step; large batches of short streams -- TCPSEG_SHORT_MIN streams or more, at
-// most TCPSEG_SHORT_SEGS slots reserved a stream on average -- one wave per stream and
-// TCPSEG_SHORT_U slots per step: there the per-stream latency chain (descriptor, template, first
-// loads, reduction, headers) is what occupancy has to hide.  Measured for this kernel
-// (profiles/tcpseg/ab_shapes.txt): the two shapes and TCPSEG_SHORT_U = 1 / 2 / 3 at ONE point, 29360
-// streams of 7 segments.  NOT measured for it: the two thresholds where the launcher changes shape;
-// they are the fragmentation kernel's values, taken over as they stand.
-constexpr uint32_t TCPSEG_SHORT_MIN = 3072u;
-constexpr uint32_t TCPSEG_SHORT_SEGS = 16u;
+// Launch shapes, the fragmentation kernel's two (the thresholds: SHORT_GROUPS_MIN /
+// SHORT_SLOTS_AVG, pico_csum_dev.h).  Four waves per stream and three 64-unit rows per step; large
+// batches of short streams one wave per stream and TCPSEG_SHORT_U rows per step.  Measured for this
+// kernel (profiles/tcpseg/ab_shapes.txt): the two shapes and TCPSEG_SHORT_U = 1 / 2 / 3 at ONE
+// point, 29360 streams of 7 segments.
 constexpr uint32_t TCPSEG_SHORT_U = 1u;
-
-__device__ __forceinline__ uint32_t bswap16(uint32_t v) { return ((v & 0xFFu) << 8) | ((v >> 8) & 0xFFu); }
-
-__device__ __forceinline__ uint4 load_una(const uint8_t* p) {
-    uint4 v;
-    __builtin_memcpy(&v, p, 16);
-    return v;
-}
-
-__device__ __forceinline__ uint32_t word_of(const uint4& v, uint32_t q) { return sel4(q, v.x, v.y, v.z, v.w); }
 
 __device__ __forceinline__ uint32_t halves(uint32_t w, bool lo, bool hi) {
     return (lo ? w & 0xFFFFu : 0u) + (hi ? w >> 16 : 0u);
 }
 
-// TSG_WAVES waves per stream, TSG_U 64-unit slots per step (3: two 1448-byte payloads)
+// TSG_WAVES waves per stream, TSG_U 64-unit rows per step (3: two 1448-byte payloads)
 template <uint32_t TSG_WAVES, uint32_t TSG_U>
 __global__ __launch_bounds__(64 * TSG_WAVES) void tcp_segment_kernel(TcpSegArgs p) {
     const uint32_t g = blockIdx.x;
@@ -93,7 +71,7 @@ __global__ __launch_bounds__(64 * TSG_WAVES) void tcp_segment_kernel(TcpSegArgs 
 
     // ---- checks (workgroup-uniform, in an order that never reads past d.len): nothing is stored
     // for a stream that fails one
-    const bool slots_in = first <= p.n_seg && reserved <= p.n_seg - first;
+    const bool slots_ok = slots_in(first, reserved, p.n_seg);
     bool bad = d.off > p.base_len || d.len > p.base_len - d.off || d.len < 1u;
     const uint8_t* h = p.base + d.off;
     uint32_t N = 20u, thl = 20u;
@@ -115,21 +93,12 @@ __global__ __launch_bounds__(64 * TSG_WAVES) void tcp_segment_kernel(TcpSegArgs 
     bad = bad || per == 0u;
     const uint32_t seg0 = min(per, P);                              // the longest segment's payload
     bad = bad || (uint64_t)(v6 ? thl : H) + seg0 > 65535u || (uint64_t)H + seg0 > p.stride;
-    const uint32_t count = bad ? 0u : (P <= per ? 1u : (uint32_t)(((uint64_t)P + per - 1u) / per));
-    const uint32_t last_pl = bad ? 0u : (uint32_t)(P - (uint64_t)(count - 1u) * per);
-    const uint64_t need = bad ? 0u : (uint64_t)(count - 1u) * p.stride + H + last_pl;
-    bad = bad || reserved < count || !slots_in || od.off > p.out_len || od.len > p.out_len - od.off || need > od.len;
+    const SlotPlan sp = bad ? SlotPlan{0u, 0u, 0u} : slot_plan(P, per, p.stride, H, P <= per);
+    const uint32_t count = sp.count, last_pl = sp.last_pl;
+    bad = bad || reserved < count || !slots_ok || od.off > p.out_len || od.len > p.out_len - od.off || sp.need > od.len;
 
-    if (p.o_seg && slots_in) {                                      // the group's slots: descriptors, then {0, 0, 0}
-        for (uint32_t k = tid; k < reserved; k += 64u * TSG_WAVES) {
-            pico_csum_desc_dev f{0, 0, 0};
-            if (!bad && k < count) {
-                f.off = od.off + (uint64_t)k * p.stride;
-                f.len = H + (k + 1u < count ? per : last_pl);
-            }
-            p.o_seg[first + k] = f;
-        }
-    }
+    if (p.o_seg && slots_ok)
+        write_slots(p.o_seg + first, reserved, bad ? 0u : count, od.off, p.stride, H, per, last_pl, tid, 64u * TSG_WAVES);
     if (tid == 0) {
         if (p.o_count) p.o_count[g] = bad ? 0u : count;
         if (p.verdict) p.verdict[g] = (uint8_t)(bad ? V_MALFORMED : V_ACCEPT);
@@ -146,10 +115,10 @@ __global__ __launch_bounds__(64 * TSG_WAVES) void tcp_segment_kernel(TcpSegArgs 
     const uint32_t a_part = (v6 ? lane >= 2u && lane < 10u : lane >= 3u && lane < 5u) ? halves(tw, true, true) : 0u;
     // TCP header without seq (word 1) and crc (word 4 low)
     const uint32_t t_part = lane >= tw0 && lane < nw ? halves(tw, j != 1u && j != 4u, j != 1u) : 0u;
-    const uint32_t nsum = (uint32_t)__builtin_amdgcn_readlane((int)group_sum<64>(n_part), 63);
+    const uint32_t nsum = wave_total(n_part);
     // the pseudo header's constant part (struct pico_ipv4_pseudo_hdr / pico_ipv6_pseudo_hdr as LE
     // words: the addresses, proto 6) and the TCP header's
-    const uint32_t csum = (uint32_t)__builtin_amdgcn_readlane((int)group_sum<64>(a_part + t_part), 63) + (6u << 8);
+    const uint32_t csum = wave_total(a_part + t_part) + (6u << 8);
     const uint32_t id0 = bswap16((uint32_t)__builtin_amdgcn_readlane((int)tw, 1) & 0xFFFFu);
     const uint32_t seq0 = __builtin_bswap32((uint32_t)__builtin_amdgcn_readlane((int)tw, (int)(tw0 + 1u)));
 
@@ -163,61 +132,12 @@ __global__ __launch_bounds__(64 * TSG_WAVES) void tcp_segment_kernel(TcpSegArgs 
         const bool hasB = kB < count;
         const uint32_t plA = kA + 1u < count ? per : last_pl, plB = hasB ? (kB + 1u < count ? per : last_pl) : 0u;
         const uint64_t dA = D + (uint64_t)kA * p.stride, dB = D + (uint64_t)kB * p.stride;
-        const uint32_t oA = (uint32_t)(dA + H) & 15u, oB = (uint32_t)(dB + H) & 15u;
-        const uint32_t nuA = (oA + plA + 15u) >> 4, nuB = hasB ? (oB + plB + 15u) >> 4 : 0u, nt = nuA + nuB;
         const uint64_t sA = S + (uint64_t)kA * per, sB = S + (uint64_t)kB * per;
 
         uint32_t accA = 0, accB = 0;
-        for (uint32_t x0 = 0; x0 < nt; x0 += 64u * TSG_U) {
-            uint4 c[TSG_U];
-            uint32_t lo[TSG_U], hi[TSG_U], od16[TSG_U];
-            bool inb[TSG_U];
-            uint64_t dst[TSG_U];
-#pragma unroll
-            for (uint32_t q = 0; q < TSG_U; ++q) {
-                const uint32_t x = x0 + 64u * q + lane;
-                inb[q] = x >= nuA;
-                const uint32_t u = inb[q] ? x - nuA : x, o = inb[q] ? oB : oA, pl = inb[q] ? plB : plA;
-                // the unit's segment bytes are [lo, hi) of its 16
-                lo[q] = u == 0u ? o : 0u;
-                hi[q] = x < nt ? (uint32_t)min(16, max((int)(o + pl) - (int)(16u * u), 0)) : 0u;
-                od16[q] = o & 1u;
-                dst[q] = (inb[q] ? dB : dA) + H + 16u * u - o;                       // 16-byte aligned
-                const uint64_t src = (inb[q] ? sB : sA) + 16u * u - o;               // >= the template's byte 25
-                c[q] = make_uint4(0, 0, 0, 0);
-                if (hi[q] > lo[q]) {
-                    if (src + 16u <= a1) {
-                        c[q] = load_una(reinterpret_cast<const uint8_t*>(src));
-                    } else {                                                         // the stream's last unit
-                        uint32_t w[4] = {0, 0, 0, 0};
-                        for (uint32_t i = lo[q]; i < hi[q]; ++i) {
-                            const uint32_t byte = (uint32_t)*reinterpret_cast<const uint8_t*>(src + i) << (8u * (i & 3u));
-                            w[0] |= (i >> 2) == 0u ? byte : 0u;
-                            w[1] |= (i >> 2) == 1u ? byte : 0u;
-                            w[2] |= (i >> 2) == 2u ? byte : 0u;
-                            w[3] |= (i >> 2) == 3u ? byte : 0u;
-                        }
-                        c[q] = make_uint4(w[0], w[1], w[2], w[3]);
-                    }
-                }
-            }
-#pragma unroll
-            for (uint32_t q = 0; q < TSG_U; ++q) {
-                if (hi[q] <= lo[q]) continue;
-                uint8_t* t = reinterpret_cast<uint8_t*>(dst[q]);
-                if (lo[q] == 0u && hi[q] == 16u) {
-                    *reinterpret_cast<uint4*>(t) = c[q];
-                } else {
-                    for (uint32_t i = lo[q]; i < hi[q]; ++i) t[i] = (uint8_t)(word_of(c[q], i >> 2) >> (8u * (i & 3u)));
-                }
-                // byte i of the unit is the segment's payload byte 16 u - o + i: an odd o swaps the pairing
-                const uint32_t s = masked_chunk_sum<true>(c[q], 0u, lo[q], hi[q], od16[q] ? SEL_ODD : SEL_EVEN);
-                accA += inb[q] ? 0u : s;
-                accB += inb[q] ? s : 0u;
-            }
-        }
-        const uint32_t payA = (uint32_t)__builtin_amdgcn_readlane((int)group_sum<64>(accA), 63);
-        const uint32_t payB = (uint32_t)__builtin_amdgcn_readlane((int)group_sum<64>(accB), 63);
+        unit_pair_move<TSG_U, false, true>(sA, sB, dA + H, dB + H, a1, a1, plA, plB, hasB, lane, accA, accB);
+        const uint32_t payA = wave_total(accA);
+        const uint32_t payB = wave_total(accB);
 
         // the headers: the template's words with the segment's own fields
         if (lane < nw) {
@@ -266,7 +186,7 @@ int pico_csum_launch_tcp_segment(const void* base, uint64_t base_len, const void
                  groups, n_seg, stride, static_cast<uint8_t*>(out), out_len,
                  static_cast<const pico_csum_desc_dev*>(out_desc), static_cast<pico_csum_desc_dev*>(o_seg), o_count,
                  verdict};
-    if (n_stream >= TCPSEG_SHORT_MIN && (uint64_t)n_seg <= (uint64_t)TCPSEG_SHORT_SEGS * n_stream)
+    if (n_stream >= SHORT_GROUPS_MIN && (uint64_t)n_seg <= (uint64_t)SHORT_SLOTS_AVG * n_stream)
         hipLaunchKernelGGL((tcp_segment_kernel<1u, TCPSEG_SHORT_U>), dim3(n_stream), dim3(64), 0,
                            static_cast<hipStream_t>(stream), a);
     else
