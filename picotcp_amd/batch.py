@@ -69,15 +69,75 @@ def _require_device(t: torch.Tensor, name: str) -> None:
 
 
 def _check_out(out: torch.Tensor, n: int, name: str, device, itemsize: int = 2) -> None:
-    """A caller-supplied result tensor: on the batch's device, contiguous, the right
-    element size and at least n elements (the kernels write n results through its pointer)."""
-    _require_device(out, name)
+    """A caller-supplied result tensor: on the batch's device (a HIP device: `base` is on it),
+    contiguous, the right element size and at least n elements (the kernels write n results through
+    its pointer)."""
     if out.device != device:
         raise ValueError(f"{name} is on {out.device}, the batch on {device}")
     if not out.is_contiguous() or out.element_size() != itemsize:
         raise ValueError(f"{name} must be a contiguous tensor of {itemsize}-byte elements")
     if out.numel() < n:
         raise ValueError(f"{name} has {out.numel()} elements, the batch {n}")
+
+
+def _require_u8(t: torch.Tensor, name: str) -> None:
+    if t.dtype != torch.uint8 or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous uint8 tensor")
+
+
+def _on_batch_device(base: torch.Tensor, **tensors):
+    """`base` is a device tensor and every named tensor is on its device, which is returned."""
+    _require_device(base, "base")
+    dev = base.device
+    for name, t in tensors.items():
+        if t.device != dev:
+            raise ValueError(f"{name} is on {t.device}, the batch on {dev}")
+    return dev
+
+
+def _pairs(t: torch.Tensor, name: str, n: int | None = None) -> int:
+    """A contiguous tensor of 4-byte elements holding one pair per group; returns the pairs it holds.
+    n=None is the tensor the batch takes its group count FROM (`groups`: n = numel // 2, so no count
+    could be wrong); n given is a tensor that must hold a pair for each of those n groups (`conn`)."""
+    if t.element_size() != 4 or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous 32-bit tensor of one pair per group")
+    if n is not None and t.numel() < 2 * n:
+        raise ValueError(f"{name} holds {t.numel() // 2} pairs, the batch has {n} groups")
+    return t.numel() // 2
+
+
+def _desc_bytes(t: torch.Tensor, count: int, name: str, by_element: bool = False) -> None:
+    """A descriptor tensor of at least 16 * count bytes.  by_element: the rule of the wrappers older than
+    the scatter/gather batches, 16 * count ELEMENTS -- the same thing for a uint8 tensor, 8 times the
+    bytes for an int64 one.  It is kept as those wrappers have it, not folded into the byte rule."""
+    if (t.numel() if by_element else t.numel() * t.element_size()) < 16 * count:
+        raise ValueError(f"{name} is shorter than {count} 16-byte descriptors")
+
+
+def _opt_desc_out(t: torch.Tensor | None, count: int, name: str, device) -> None:
+    """The optional descriptor output of a scatter batch (out_frag / out_seg), when given."""
+    if t is None:
+        return
+    if t.device != device or not t.is_contiguous() or t.numel() * t.element_size() < 16 * count:
+        raise ValueError(f"{name} must be a contiguous tensor of {count} 16-byte descriptors on the batch's device")
+
+
+def _results(results, spec, counts, device) -> tuple:
+    """A wrapper's result tensors, in return order: spec = (name, dtype, itemsize, optional) per member
+    (a constant beside its wrapper), counts = each member's elements.  None allocates them all; a
+    caller's own are checked (_check_out), an optional member may be None (the library skips that
+    output)."""
+    if results is None:
+        return tuple(torch.empty(count, dtype=dtype, device=device) for (_, dtype, _, _), count in zip(spec, counts))
+    for t, (name, _, itemsize, optional), count in zip(results, spec, counts):
+        if t is not None or not optional:
+            _check_out(t, count, name, device, itemsize)
+    return results if type(results) is tuple else tuple(results)
+
+
+# the fused checksum batches' (out_net, out_transport, verdict); the IPv6 batch returns the last two
+_CHECKSUM_OUTS = (("out_net", torch.int16, 2, False), ("out_transport", torch.int16, 2, False), ("verdict", torch.uint8, 1, False))
+_CHECKSUM6_OUTS = _CHECKSUM_OUTS[1:]
 
 
 def checksum_uniform(base: torch.Tensor, stride: int, length: int, n: int, seed: int = 0,
@@ -104,8 +164,7 @@ def checksum_batch(base: torch.Tensor, desc: torch.Tensor, n: int, crc_off: int 
     read (out 0); `bad` (int32[1] on the device) counts them when given."""
     _require_device(base, "base")
     _require_device(desc, "desc")
-    if desc.numel() < 16 * n:
-        raise ValueError("descriptor tensor shorter than n entries")
+    _desc_bytes(desc, n, "desc", by_element=True)
     if out is None:
         out = torch.empty(n, dtype=torch.int16, device=base.device)
     _check_out(out, n, "out", base.device)
@@ -124,15 +183,8 @@ def ipv4_checksum_batch(base: torch.Tensor, desc: torch.Tensor, n: int, flags: i
     that triple preallocated."""
     _require_device(base, "base")
     _require_device(desc, "desc")
-    if desc.numel() < 16 * n:
-        raise ValueError("descriptor tensor shorter than n entries")
-    dev = base.device
-    if out is None:
-        out = (torch.empty(n, dtype=torch.int16, device=dev), torch.empty(n, dtype=torch.int16, device=dev),
-               torch.empty(n, dtype=torch.uint8, device=dev))
-    out_net, out_l4, verdict = out
-    for t, nm, sz in ((out_net, "out_net", 2), (out_l4, "out_transport", 2), (verdict, "verdict", 1)):
-        _check_out(t, n, nm, dev, sz)
+    _desc_bytes(desc, n, "desc", by_element=True)
+    out_net, out_l4, verdict = _results(out, _CHECKSUM_OUTS, (n, n, n), base.device)
     lib = _lib.load()
     _lib.check("pico_ipv4_checksum_batch_dev",
                lib.pico_ipv4_checksum_batch_dev(_ptr(base), base.numel(), _ptr(desc), n, flags, _ptr(out_net),
@@ -147,14 +199,8 @@ def ipv6_checksum_batch(base: torch.Tensor, desc: torch.Tensor, n: int, flags: i
     preallocated."""
     _require_device(base, "base")
     _require_device(desc, "desc")
-    if desc.numel() < 16 * n:
-        raise ValueError("descriptor tensor shorter than n entries")
-    dev = base.device
-    if out is None:
-        out = (torch.empty(n, dtype=torch.int16, device=dev), torch.empty(n, dtype=torch.uint8, device=dev))
-    out_l4, verdict = out
-    for t, nm, sz in ((out_l4, "out_transport", 2), (verdict, "verdict", 1)):
-        _check_out(t, n, nm, dev, sz)
+    _desc_bytes(desc, n, "desc", by_element=True)
+    out_l4, verdict = _results(out, _CHECKSUM6_OUTS, (n, n), base.device)
     lib = _lib.load()
     _lib.check("pico_ipv6_checksum_batch_dev",
                lib.pico_ipv6_checksum_batch_dev(_ptr(base), base.numel(), _ptr(desc), n, flags, _ptr(out_l4),
@@ -181,17 +227,10 @@ def eth_checksum_batch(base: torch.Tensor, desc: torch.Tensor, n: int, flags: in
     Returns (out_net int16[n], out_transport int16[n], verdict uint8[n])."""
     _require_device(base, "base")
     _require_device(desc, "desc")
-    if desc.numel() < 16 * n:
-        raise ValueError("descriptor tensor shorter than n entries")
+    _desc_bytes(desc, n, "desc", by_element=True)
     if mac is not None and len(mac) != 6:
         raise ValueError("mac must be 6 bytes")
-    dev = base.device
-    if out is None:
-        out = (torch.empty(n, dtype=torch.int16, device=dev), torch.empty(n, dtype=torch.int16, device=dev),
-               torch.empty(n, dtype=torch.uint8, device=dev))
-    out_net, out_l4, verdict = out
-    for t, nm, sz in ((out_net, "out_net", 2), (out_l4, "out_transport", 2), (verdict, "verdict", 1)):
-        _check_out(t, n, nm, dev, sz)
+    out_net, out_l4, verdict = _results(out, _CHECKSUM_OUTS, (n, n, n), base.device)
     lib = _lib.load()
     m = None if mac is None else _mac_buf(bytes(mac))
     _lib.check("pico_eth_checksum_batch_dev",
@@ -222,8 +261,7 @@ def ipv4_forward_batch(base: torch.Tensor, desc: torch.Tensor, n: int, *, state:
     _require_device(base, "base")
     _require_u8(base, "base")
     _require_device(desc, "desc")
-    if desc.numel() < 16 * n:
-        raise ValueError("descriptor tensor shorter than n entries")
+    _desc_bytes(desc, n, "desc", by_element=True)
     if verdict is None:
         verdict = torch.empty(n, dtype=torch.uint8, device=base.device)
     _check_out(verdict, n, "verdict", base.device, 1)
@@ -250,27 +288,15 @@ def ipv4_nat_batch(base: torch.Tensor, desc: torch.Tensor, n: int, nat: torch.Te
     _require_u8(base, "base")
     _require_device(desc, "desc")
     _require_device(nat, "nat")
-    if desc.numel() < 16 * n:
-        raise ValueError("descriptor tensor shorter than n entries")
+    _desc_bytes(desc, n, "desc", by_element=True)
     if nat.numel() * nat.element_size() < 8 * n or not nat.is_contiguous():
         raise ValueError("nat must be a contiguous tensor of n 8-byte records")
-    dev = base.device
-    if out is None:
-        out = (torch.empty(n, dtype=torch.int16, device=dev), torch.empty(n, dtype=torch.int16, device=dev),
-               torch.empty(n, dtype=torch.uint8, device=dev))
-    out_net, out_l4, verdict = out
-    for t, nm, sz in ((out_net, "out_net", 2), (out_l4, "out_transport", 2), (verdict, "verdict", 1)):
-        _check_out(t, n, nm, dev, sz)
+    out_net, out_l4, verdict = _results(out, _CHECKSUM_OUTS, (n, n, n), base.device)
     lib = _lib.load()
     _lib.check("pico_ipv4_nat_batch_dev",
                lib.pico_ipv4_nat_batch_dev(_ptr(base), base.numel(), _ptr(desc), n, _ptr(nat), _ptr(out_net),
                                            _ptr(out_l4), _ptr(verdict), _stream_handle(stream)))
     return out_net, out_l4, verdict
-
-
-def _require_u8(t: torch.Tensor, name: str) -> None:
-    if t.dtype != torch.uint8 or not t.is_contiguous():
-        raise ValueError(f"{name} must be a contiguous uint8 tensor")
 
 
 def ipv4_reassemble_batch(base: torch.Tensor, frag_desc: torch.Tensor, n_frag: int, groups: torch.Tensor,
@@ -289,25 +315,17 @@ def ipv6_reassemble_batch(base: torch.Tensor, frag_desc: torch.Tensor, n_frag: i
     return _reassemble(True, base, frag_desc, n_frag, groups, out, out_desc, flags, stream, results)
 
 
+_REASSEMBLE_OUTS = (("out_len", torch.int32, 4, False), ("out_transport", torch.int16, 2, False), ("verdict", torch.uint8, 1, False))
+
+
 def _reassemble(v6, base, frag_desc, n_frag, groups, out, out_desc, flags, stream, results):
-    for t, nm in ((base, "base"), (frag_desc, "frag_desc"), (groups, "groups"), (out, "out"), (out_desc, "out_desc")):
-        _require_device(t, nm)
-        if t.device != base.device:
-            raise ValueError(f"{nm} is on {t.device}, the batch on {base.device}")
+    dev = _on_batch_device(base, frag_desc=frag_desc, groups=groups, out=out, out_desc=out_desc)
     _require_u8(base, "base")
     _require_u8(out, "out")
-    n = groups.numel() // 2
-    if groups.element_size() != 4 or not groups.is_contiguous():
-        raise ValueError("groups must be a contiguous 32-bit tensor of (first, count) pairs")
-    if frag_desc.numel() * frag_desc.element_size() < 16 * n_frag or out_desc.numel() * out_desc.element_size() < 16 * n:
-        raise ValueError("descriptor tensor shorter than its count")
-    dev = base.device
-    if results is None:
-        results = (torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int16, device=dev),
-                   torch.empty(n, dtype=torch.uint8, device=dev))
-    ol, l4, v = results
-    for t, nm, sz in ((ol, "out_len", 4), (l4, "out_transport", 2), (v, "verdict", 1)):
-        _check_out(t, n, nm, dev, sz)
+    n = _pairs(groups, "groups")
+    _desc_bytes(frag_desc, n_frag, "frag_desc")
+    _desc_bytes(out_desc, n, "out_desc")
+    ol, l4, v = _results(results, _REASSEMBLE_OUTS, (n, n, n), dev)
     lib = _lib.load()
     if v6:
         _lib.check("pico_ipv6_reassemble_batch_dev",
@@ -322,6 +340,10 @@ def _reassemble(v6, base, frag_desc, n_frag, groups, out, out_desc, flags, strea
     return ol, l4, v
 
 
+_FRAGMENT_OUTS = (("verdict", torch.uint8, 1, True), ("count", torch.int32, 4, True), ("out_transport", torch.int16, 2, True))
+_SEGMENT_OUTS = _FRAGMENT_OUTS[:2]
+
+
 def ipv4_fragment_batch(base: torch.Tensor, dgram_desc: torch.Tensor, mtu: int, groups: torch.Tensor, n_frag: int,
                         out: torch.Tensor, out_desc: torch.Tensor, frag_stride: int, flags: int = 0,
                         out_frag: torch.Tensor | None = None, stream=None, results=None):
@@ -334,29 +356,14 @@ def ipv4_fragment_batch(base: torch.Tensor, dgram_desc: torch.Tensor, mtu: int, 
     tensor of 16*n_frag bytes, or None) receives the fragments' descriptors.  flags: F_WRITE stores
     the transport checksum into its crc field.  Returns (verdict uint8[n], count int32[n],
     out_transport int16[n]); `results` may pass that triple preallocated, any of them None to skip it."""
-    for t, nm in ((base, "base"), (dgram_desc, "dgram_desc"), (groups, "groups"), (out, "out"), (out_desc, "out_desc")):
-        _require_device(t, nm)
-        if t.device != base.device:
-            raise ValueError(f"{nm} is on {t.device}, the batch on {base.device}")
+    dev = _on_batch_device(base, dgram_desc=dgram_desc, groups=groups, out=out, out_desc=out_desc)
     _require_u8(base, "base")
     _require_u8(out, "out")
-    n = groups.numel() // 2
-    if groups.element_size() != 4 or not groups.is_contiguous():
-        raise ValueError("groups must be a contiguous 32-bit tensor of (first, reserved) pairs")
-    if dgram_desc.numel() * dgram_desc.element_size() < 16 * n or out_desc.numel() * out_desc.element_size() < 16 * n:
-        raise ValueError("descriptor tensor shorter than its count")
-    dev = base.device
-    if out_frag is not None:
-        _require_device(out_frag, "out_frag")
-        if out_frag.device != dev or not out_frag.is_contiguous() or out_frag.numel() * out_frag.element_size() < 16 * n_frag:
-            raise ValueError("out_frag must be a contiguous tensor of n_frag 16-byte descriptors on the batch's device")
-    if results is None:
-        results = (torch.empty(n, dtype=torch.uint8, device=dev), torch.empty(n, dtype=torch.int32, device=dev),
-                   torch.empty(n, dtype=torch.int16, device=dev))
-    v, cnt, l4 = results
-    for t, nm, sz in ((v, "verdict", 1), (cnt, "count", 4), (l4, "out_transport", 2)):
-        if t is not None:
-            _check_out(t, n, nm, dev, sz)
+    n = _pairs(groups, "groups")
+    _desc_bytes(dgram_desc, n, "dgram_desc")
+    _desc_bytes(out_desc, n, "out_desc")
+    _opt_desc_out(out_frag, n_frag, "out_frag", dev)
+    v, cnt, l4 = _results(results, _FRAGMENT_OUTS, (n, n, n), dev)
     lib = _lib.load()
     _lib.check("pico_ipv4_fragment_batch_dev",
                lib.pico_ipv4_fragment_batch_dev(_ptr(base), base.numel(), _ptr(dgram_desc), n, mtu, _ptr(groups), n_frag,
@@ -378,34 +385,23 @@ def tcp_segment_batch(base: torch.Tensor, stream_desc: torch.Tensor, groups: tor
     receives the segments' descriptors -- with `out`, the input of ipv4_checksum_batch /
     ipv6_checksum_batch.  flags: reserved, 0.  Returns (verdict uint8[n], count int32[n]); `results`
     may pass that pair preallocated, either of them None to skip it."""
-    for t, nm in ((base, "base"), (stream_desc, "stream_desc"), (groups, "groups"), (out, "out"), (out_desc, "out_desc")):
-        _require_device(t, nm)
-        if t.device != base.device:
-            raise ValueError(f"{nm} is on {t.device}, the batch on {base.device}")
+    dev = _on_batch_device(base, stream_desc=stream_desc, groups=groups, out=out, out_desc=out_desc)
     _require_u8(base, "base")
     _require_u8(out, "out")
-    n = groups.numel() // 2
-    if groups.element_size() != 4 or not groups.is_contiguous():
-        raise ValueError("groups must be a contiguous 32-bit tensor of (first, reserved) pairs")
-    if stream_desc.numel() * stream_desc.element_size() < 16 * n or out_desc.numel() * out_desc.element_size() < 16 * n:
-        raise ValueError("descriptor tensor shorter than its count")
-    dev = base.device
-    if out_seg is not None:
-        _require_device(out_seg, "out_seg")
-        if out_seg.device != dev or not out_seg.is_contiguous() or out_seg.numel() * out_seg.element_size() < 16 * n_seg:
-            raise ValueError("out_seg must be a contiguous tensor of n_seg 16-byte descriptors on the batch's device")
-    if results is None:
-        results = (torch.empty(n, dtype=torch.uint8, device=dev), torch.empty(n, dtype=torch.int32, device=dev))
-    v, cnt = results
-    for t, nm, sz in ((v, "verdict", 1), (cnt, "count", 4)):
-        if t is not None:
-            _check_out(t, n, nm, dev, sz)
+    n = _pairs(groups, "groups")
+    _desc_bytes(stream_desc, n, "stream_desc")
+    _desc_bytes(out_desc, n, "out_desc")
+    _opt_desc_out(out_seg, n_seg, "out_seg", dev)
+    v, cnt = _results(results, _SEGMENT_OUTS, (n, n), dev)
     lib = _lib.load()
     _lib.check("pico_tcp_segment_batch_dev",
                lib.pico_tcp_segment_batch_dev(_ptr(base), base.numel(), _ptr(stream_desc), n, _ptr(groups), n_seg,
                                               _ptr(out), out.numel(), _ptr(out_desc), seg_stride, _ptr(out_seg),
                                               _ptr(cnt), _ptr(v), flags, _stream_handle(stream)))
     return v, cnt
+
+
+_COALESCE_OUTS = (("verdict", torch.uint8, 1, True), ("out_len", torch.int32, 4, True), ("seg_verdict", torch.uint8, 1, True))
 
 
 def tcp_coalesce_batch(base: torch.Tensor, seg_desc: torch.Tensor, n_seg: int, groups: torch.Tensor,
@@ -423,27 +419,14 @@ def tcp_coalesce_batch(base: torch.Tensor, seg_desc: torch.Tensor, n_seg: int, g
     bytes delivered (the new rcv_nxt is rcv_nxt + out_len), and per segment V_ACCEPT, V_NET_BAD,
     V_L4_BAD, V_MALFORMED, V_FRAG, V_TCP_CTRL, V_TCP_OLD or V_TCP_HELD; `results` may pass that triple
     preallocated, any of them None to skip it."""
-    for t, nm in ((base, "base"), (seg_desc, "seg_desc"), (groups, "groups"), (conn, "conn"), (out, "out"),
-                  (out_desc, "out_desc")):
-        _require_device(t, nm)
-        if t.device != base.device:
-            raise ValueError(f"{nm} is on {t.device}, the batch on {base.device}")
+    dev = _on_batch_device(base, seg_desc=seg_desc, groups=groups, conn=conn, out=out, out_desc=out_desc)
     _require_u8(base, "base")
     _require_u8(out, "out")
-    n = groups.numel() // 2
-    for t, nm in ((groups, "groups"), (conn, "conn")):
-        if t.element_size() != 4 or not t.is_contiguous() or t.numel() < 2 * n:
-            raise ValueError(f"{nm} must be a contiguous 32-bit tensor of one pair per connection")
-    if seg_desc.numel() * seg_desc.element_size() < 16 * n_seg or out_desc.numel() * out_desc.element_size() < 16 * n:
-        raise ValueError("descriptor tensor shorter than its count")
-    dev = base.device
-    if results is None:
-        results = (torch.empty(n, dtype=torch.uint8, device=dev), torch.empty(n, dtype=torch.int32, device=dev),
-                   torch.empty(n_seg, dtype=torch.uint8, device=dev))
-    v, ol, sv = results
-    for t, nm, cnt, sz in ((v, "verdict", n, 1), (ol, "out_len", n, 4), (sv, "seg_verdict", n_seg, 1)):
-        if t is not None:
-            _check_out(t, cnt, nm, dev, sz)
+    n = _pairs(groups, "groups")
+    _pairs(conn, "conn", n)
+    _desc_bytes(seg_desc, n_seg, "seg_desc")
+    _desc_bytes(out_desc, n, "out_desc")
+    v, ol, sv = _results(results, _COALESCE_OUTS, (n, n, n_seg), dev)
     lib = _lib.load()
     _lib.check("pico_tcp_coalesce_batch_dev",
                lib.pico_tcp_coalesce_batch_dev(_ptr(base), base.numel(), _ptr(seg_desc), n_seg, _ptr(groups), _ptr(conn), n,

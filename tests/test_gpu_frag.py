@@ -14,7 +14,7 @@ from oracle import oracle as O
 from picotcp_amd import batch, synth
 from tests import golden_data as G
 from tests.test_frag_oracle import MF, frame, run
-from tests.test_gpu_parity import to_dev
+from tests.gpu_util import pairs_dev, to_dev
 
 pytestmark = pytest.mark.gpu
 
@@ -32,7 +32,7 @@ def reasm_path(request):
 def gpu_reassemble(buf, d, grp, od, out_size, v6=False, nx=False):
     out = torch.zeros(out_size, dtype=torch.uint8, device="cuda:0")
     args = (buf if isinstance(buf, torch.Tensor) else to_dev(buf), to_dev(d.view(np.uint8)), d.size,
-            to_dev(np.ascontiguousarray(grp, np.uint32).reshape(-1).view(np.int32)), out, to_dev(od.view(np.uint8)))
+            pairs_dev(grp), out, to_dev(od.view(np.uint8)))
     if v6:
         ol, l4, v = batch.ipv6_reassemble_batch(*args, flags=batch.F_NXTHDR_DISPATCH if nx else 0)
     else:
@@ -230,8 +230,7 @@ def _flat_case(n, seed):
     od, size = layout(lens, shift=4)
     out_o = np.zeros(size, np.uint8)
     want = O.ipv4_reassemble(buf, d, grp, out_o, od)
-    dev = (to_dev(buf), to_dev(d.view(np.uint8)), d.size,
-           to_dev(np.ascontiguousarray(grp, np.uint32).reshape(-1).view(np.int32)), to_dev(od.view(np.uint8)))
+    dev = (to_dev(buf), to_dev(d.view(np.uint8)), d.size, pairs_dev(grp), to_dev(od.view(np.uint8)))
     return dev, od, size, want, out_o
 
 

@@ -14,19 +14,11 @@ from oracle import oracle as O
 from picotcp_amd import batch, synth
 from tests import fragtx_ref as R
 from tests import test_ref_fragtx as RF
+from tests.gpu_util import DEV, pairs_dev as grp_dev, replay_captured, to_dev
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 CANARY = 0xA5
-
-
-def to_dev(a: np.ndarray) -> torch.Tensor:
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def grp_dev(groups: np.ndarray) -> torch.Tensor:
-    return to_dev(np.ascontiguousarray(groups, np.uint32).reshape(-1).view(np.int32))
 
 
 def gpu_fragment(base, dd, mtu, groups, n_frag, out_size, od, stride, flags=0):
@@ -244,25 +236,24 @@ def test_graph_replay():
     of = torch.zeros(16 * n_frag, dtype=torch.uint8, device=DEV)
     res = batch.ipv4_fragment_batch(*args, out, d_od, 1536, flags=batch.F_WRITE, out_frag=of)      # warm (eager)
     torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        with torch.cuda.graph(g, stream=s):
-            batch.ipv4_fragment_batch(*args, out, d_od, 1536, flags=batch.F_WRITE, out_frag=of, stream=s, results=res)
-    torch.cuda.current_stream().wait_stream(s)
-    for _ in range(2):
+
+    def call(s):
+        batch.ipv4_fragment_batch(*args, out, d_od, 1536, flags=batch.F_WRITE, out_frag=of, stream=s, results=res)
+
+    def reset():
         out.fill_(CANARY)
         of.zero_()
         for r in res:
             r.zero_()
-        g.replay()
-        torch.cuda.synchronize()
+
+    def same():
         np.testing.assert_array_equal(out.cpu().numpy(), want_out)
         np.testing.assert_array_equal(of.cpu().numpy().view(R.DESC_DTYPE), wof)
         np.testing.assert_array_equal(res[0].cpu().numpy(), wv)
         np.testing.assert_array_equal(res[1].cpu().numpy().view(np.uint32), wc)
         np.testing.assert_array_equal(res[2].cpu().numpy().view(np.uint16), w4)
+
+    replay_captured(call, reset, same)
 
 
 def test_large_batch_one_wave_per_datagram():

@@ -11,9 +11,9 @@ import torch
 
 from oracle import oracle as O
 from picotcp_amd import batch, synth
+from tests.gpu_util import DEV, to_dev
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 
 
 @pytest.fixture(autouse=True)
@@ -25,10 +25,6 @@ def _reset_override():
 def u16(t):
     torch.cuda.synchronize()
     return t.cpu().numpy().view(np.uint16)
-
-
-def to_dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 # descriptor batches: the sorted-rounds kernel, automatic or with forced frames per wave

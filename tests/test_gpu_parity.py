@@ -9,10 +9,10 @@ import torch
 from oracle import oracle as O
 from picotcp_amd import batch, synth
 from tests import golden_data as G
+from tests.gpu_util import DEV, to_dev
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 SHAPES = [(g, c) for g in (4, 8, 16, 32, 64) for c in (1, 2, 4, 8)] + \
     [(g, c) for g in (8, 16, 32, 64) for c in (3, 5, 6, 7)]     # (the pipelined kernel's extra shapes)
 # descriptor batches: the sorted-rounds kernel, automatic or with a forced frames-per-wave
@@ -31,10 +31,6 @@ def use_kernel(name):
 def u16(t: torch.Tensor) -> np.ndarray:
     torch.cuda.synchronize()
     return t.cpu().numpy().view(np.uint16)
-
-
-def to_dev(a: np.ndarray) -> torch.Tensor:
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 @pytest.fixture(autouse=True)

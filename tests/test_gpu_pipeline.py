@@ -19,7 +19,7 @@ import torch
 
 from oracle import oracle as O
 from picotcp_amd import batch, synth
-from tests.test_gpu_parity import to_dev
+from tests.gpu_util import pairs_dev, to_dev
 
 pytestmark = pytest.mark.gpu
 
@@ -129,7 +129,7 @@ def test_rx_reassembly_nat_pipeline():
     out = torch.zeros(ng * cap, dtype=torch.uint8, device="cuda:0")
     rl, rl4, rv = batch.ipv4_reassemble_batch(
         d_ring, batch.desc_to_device(fdesc, "cuda:0"), len(fd),
-        to_dev(np.array(groups, np.uint32).reshape(-1).view(np.int32)), out, batch.desc_to_device(od, "cuda:0"))
+        pairs_dev(groups), out, batch.desc_to_device(od, "cuda:0"))
     torch.cuda.synchronize()
     rv, rl, out_h = rv.cpu().numpy(), rl.cpu().numpy().view(np.uint32), out.cpu().numpy()
     assert ng == len(big) and (rv == batch.V_ACCEPT).all()

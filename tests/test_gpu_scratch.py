@@ -13,7 +13,7 @@ from oracle import oracle as O
 from picotcp_amd import _lib, batch
 from tests import golden_data as G
 from tests.test_gpu_frag import layout
-from tests.test_gpu_parity import to_dev
+from tests.gpu_util import pairs_dev, to_dev
 
 pytestmark = pytest.mark.gpu
 
@@ -45,8 +45,7 @@ def _make():
     od, size = layout([8] * N, shift=4)
     want = O.ipv4_reassemble(buf, d, grp, np.zeros(size, np.uint8), od)
     assert (want[2] == 1).all()
-    dev = (to_dev(buf), to_dev(d.view(np.uint8)), d.size,
-           to_dev(np.ascontiguousarray(grp, np.uint32).reshape(-1).view(np.int32)), to_dev(od.view(np.uint8)))
+    dev = (to_dev(buf), to_dev(d.view(np.uint8)), d.size, pairs_dev(grp), to_dev(od.view(np.uint8)))
     return dev, size, want
 
 

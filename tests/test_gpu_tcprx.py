@@ -14,21 +14,13 @@ import torch
 from picotcp_amd import batch, synth
 from tests import tcprx_ref as R
 from tests import test_ref_tcprx as RF
+from tests.gpu_util import DEV, pairs_dev, replay_captured, to_dev
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 CANARY = 0xA5
 A, NB, LB, MF, FR, CT, OL, HE = (R.V_ACCEPT, R.V_NET_BAD, R.V_L4_BAD, R.V_MALFORMED, R.V_FRAG, R.V_TCP_CTRL, R.V_TCP_OLD,
                                  R.V_TCP_HELD)
-
-
-def to_dev(a: np.ndarray) -> torch.Tensor:
-    return torch.from_numpy(np.array(a, copy=True, order="C")).to(DEV)      # (a copy: the fixture's arrays are read-only)
-
-
-def pairs_dev(a: np.ndarray) -> torch.Tensor:
-    return to_dev(np.ascontiguousarray(a, np.uint32).reshape(-1).view(np.int32))
 
 
 def dev_args(buf, sd, groups, conn, od):
@@ -377,23 +369,22 @@ def test_graph_replay():
     out = torch.full((out_size,), CANARY, dtype=torch.uint8, device=DEV)
     res = batch.tcp_coalesce_batch(*args, out, d_od)                        # warm (eager)
     torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        with torch.cuda.graph(g, stream=s):
-            batch.tcp_coalesce_batch(*args, out, d_od, stream=s, results=res)
-    torch.cuda.current_stream().wait_stream(s)
-    for _ in range(2):
+
+    def call(s):
+        batch.tcp_coalesce_batch(*args, out, d_od, stream=s, results=res)
+
+    def reset():
         out.fill_(CANARY)
         for r in res:
             r.zero_()
-        g.replay()
-        torch.cuda.synchronize()
+
+    def same():
         np.testing.assert_array_equal(out.cpu().numpy()[keep], want_out[keep])
         np.testing.assert_array_equal(res[0].cpu().numpy(), wv)
         np.testing.assert_array_equal(res[1].cpu().numpy().view(np.uint32), wl)
         np.testing.assert_array_equal(res[2].cpu().numpy(), ws)
+
+    replay_captured(call, reset, same)
 
 
 def test_256_connections_in_one_launch():

@@ -27,10 +27,10 @@ import torch
 
 from picotcp_amd import batch, synth
 from tests import fragtx_ref, tcprx_ref, tcpseg_ref
+from tests.gpu_util import DEV, pairs_dev, to_dev
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 CANARY = 0xA5
 ITEMS = [(m, L, o, par) for m in (1, 2, 3) for L in range(1, 49) for o in range(16) for par in (0, 1)]
 SHAPES = {"one_wave": ITEMS, "four_waves": ITEMS[::3]}      # 4608 groups: >= 3072; 1536: below
@@ -57,14 +57,6 @@ def regions(cap, first_payload_at, hdr):
         ooff[g] = pos
         pos += int(c)
     return ooff, pos + 16
-
-
-def to_dev(a: np.ndarray) -> torch.Tensor:
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def pairs_dev(a: np.ndarray) -> torch.Tensor:
-    return to_dev(np.ascontiguousarray(a, np.uint32).reshape(-1).view(np.int32))
 
 
 def same_bytes(got: np.ndarray, want: np.ndarray):

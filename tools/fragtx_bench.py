@@ -10,6 +10,8 @@ Legs, per shape (datagrams of --tl transport bytes, split at --mtu into frames -
                   the datagram to its place in the output, nothing summed, no headers (4 waves per
                   datagram as the fragment kernel, and flat: one wave per fragment pair)
   seq_copy        the device's contiguous copy of the payload bytes (seq_copy, nt loads and stores)
+Without tools/bin/libgather_ceiling.so the bare_scatter legs and seq_copy are left out, with a warning
+and a note in the JSON.  The scaffold (graphs, warm-up, timing, summary) is tools/sg_harness.py's.
 Each leg runs over --rotate buffer sets (the working set of one set already exceeds the 256 MiB
 Infinity Cache at the default shapes); one replay = one pass over every set, captured as a HIP
 graph; the figure is the median of --replays (>= 20) replays timed by HIP events, per call.
@@ -20,9 +22,7 @@ and the TCP checksum the fragment batch stored verifying (0) in the reassembly.
 """
 from __future__ import annotations
 
-import argparse
 import ctypes
-import json
 import os
 import sys
 
@@ -31,9 +31,8 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+import sg_harness as SG  # noqa: E402
 from picotcp_amd import batch, synth  # noqa: E402
-
-HBM_PEAK = 8.0e12       # MI355X HBM3E, bytes / s (datasheet)
 
 
 def make_set(n, tl, mtu, stride, dev, seed):
@@ -118,35 +117,13 @@ def run_shape(name, n, tl, a, dev, lib):
     if not ok:
         raise SystemExit(f"{name}: the fragment / reassemble round trip does not check out at the timed size")
 
+    # the legs take turns in this order, replay by replay
+    # (the bare scatter rounds its stores up past a fragment's end, into the next header: the
+    # fragment leg, which rewrites every header, always runs between it and the reassembly)
     legs = {"fragment": fragment, "reassemble": reassemble}
     if lib is not None:
         legs.update({"bare_scatter_4waves": bare(2), "bare_scatter_flat": bare(3), "seq_copy": seq})
-    graphs = {}
-    for nm, f in legs.items():
-        gph = torch.cuda.CUDAGraph()
-        cs = torch.cuda.Stream(dev)
-        cs.wait_stream(stream)
-        with torch.cuda.stream(cs):
-            with torch.cuda.graph(gph, stream=cs):
-                for s in sets:
-                    f(s, cs)
-        stream.wait_stream(cs)
-        graphs[nm] = gph
-    for _ in range(a.warmup):
-        for gph in graphs.values():
-            gph.replay()
-    torch.cuda.synchronize(dev)
-    times = {nm: [] for nm in legs}
-    # (the bare scatter rounds its stores up past a fragment's end, into the next header: the
-    # fragment leg, which rewrites every header, always runs between it and the reassembly)
-    for _ in range(a.replays):                               # the legs alternate, replay by replay
-        for nm, gph in graphs.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(stream)
-            gph.replay()
-            e1.record(stream)
-            torch.cuda.synchronize(dev)
-            times[nm].append(e0.elapsed_time(e1) * 1e3 / a.rotate)
+    times = SG.time_legs(legs, sets, dev, stream, a.warmup, a.replays, a.rotate)
     for s in sets:                                           # the timed replays worked on good data
         if not bool((s["res"][0] == batch.V_ACCEPT).all() and (s["rres"][2] == batch.V_ACCEPT).all()):
             raise SystemExit(f"{name}: a timed replay did not accept every datagram")
@@ -158,60 +135,12 @@ def run_shape(name, n, tl, a, dev, lib):
          "rotate": a.rotate, "replays": a.replays, "working_set_bytes_per_set": int(sets[0]["buf"].numel() + sets[0]["out"].numel()),
          "payload_bytes": payload, "algorithmic_bytes_read": read_b, "algorithmic_bytes_written": written_b,
          "written_over_algorithmic": round(written_b / (read_b + written_b), 4), "round_trip_checked": ok}
-    for nm, v in times.items():
-        us = float(np.median(v))
-        r[nm + "_us"] = round(us, 2)
-        r[nm + "_us_min_max"] = [round(min(v), 2), round(max(v), 2)]
-        moved = read_b + written_b if nm in ("fragment", "reassemble") else 2 * payload
-        r[nm + "_TBs"] = round(moved / us / 1e6, 3)
-        r[nm + "_fraction_of_8TBs"] = round(moved / (us * 1e-6) / HBM_PEAK, 3)
+    SG.summarise(r, times, {"fragment": read_b + written_b, "reassemble": read_b + written_b}, payload)
     r["fragment_over_reassemble"] = round(r["fragment_us"] / r["reassemble_us"], 3)
+    if lib is None:
+        r["ceiling_legs"] = SG.CEILING_NOT_MEASURED
     return r
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--shape", default="both", choices=["c3", "9000", "both"])
-    ap.add_argument("--n", type=int, default=0, help="datagrams (0: 4096 x 64512 B, or as many 9000 B ones for the same bytes)")
-    ap.add_argument("--mtu", type=int, default=1500)
-    ap.add_argument("--stride", type=int, default=1504)
-    ap.add_argument("--rotate", type=int, default=3)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--replays", type=int, default=24)
-    ap.add_argument("--out", default="")
-    a = ap.parse_args()
-    if a.replays < 20:
-        raise SystemExit("--replays: at least 20")
-    if not torch.cuda.is_available():
-        raise SystemExit("fragtx_bench.py measures on the GPU: no HIP device here (not measured)")
-    dev = torch.device("cuda:0")
-    lib = None
-    p = os.path.join(ROOT, "tools", "bin", "libgather_ceiling.so")
-    if os.path.exists(p):
-        lib = ctypes.CDLL(p)
-        lib.seq_copy_launch.restype = ctypes.c_int
-        lib.seq_copy_launch.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
-                                        ctypes.c_uint64, ctypes.c_void_p]
-        lib.gather_ceiling_launch.restype = ctypes.c_int
-        lib.gather_ceiling_launch.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64] + [ctypes.c_void_p] * 4 + \
-            [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
-    shapes = []
-    if a.shape in ("c3", "both"):
-        shapes.append(("c3_fragtx", a.n or 4096, 64512))
-    if a.shape in ("9000", "both"):
-        shapes.append(("fragtx_9000", a.n or 4096 * 64512 // 9000, 9000))
-    results = []
-    for name, n, tl in shapes:
-        r = run_shape(name, n, tl, a, dev, lib)
-        print(json.dumps(r), flush=True)
-        results.append(r)
-        torch.cuda.empty_cache()
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump({"device": torch.cuda.get_device_name(0), "results": results}, f, indent=1)
-            f.write("\n")
-
-
 if __name__ == "__main__":
-    main()
+    SG.main("fragtx_bench.py", "datagrams", (("--mtu", 1500),), ("c3_fragtx", "fragtx_9000"), run_shape)

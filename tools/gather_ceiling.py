@@ -24,6 +24,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
 from picotcp_amd import batch  # noqa: E402
+from sg_harness import load_ceiling_lib  # noqa: E402
 
 
 def main():
@@ -38,13 +39,9 @@ def main():
     a = ap.parse_args()
     batch.set_reasm_flat(a.reasm_flat)
     dev = torch.device("cuda:0")
-    lib = ctypes.CDLL(os.path.join(ROOT, "tools", "bin", "libgather_ceiling.so"))
-    lib.seq_copy_launch.restype = ctypes.c_int
-    lib.seq_copy_launch.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
-                                    ctypes.c_uint64, ctypes.c_void_p]
-    lib.gather_ceiling_launch.restype = ctypes.c_int
-    lib.gather_ceiling_launch.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64] + [ctypes.c_void_p] * 4 + \
-        [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
+    lib = load_ceiling_lib("gather_ceiling.py")
+    if lib is None:
+        raise SystemExit("gather_ceiling.py measures nothing without it")
     tl = 64512
     hl = 48 if a.v6 else 20
     H = 40 if a.v6 else 20

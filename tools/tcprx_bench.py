@@ -28,9 +28,7 @@ and the delivered bytes equal the stream's payload.
 """
 from __future__ import annotations
 
-import argparse
 import ctypes
-import json
 import os
 import sys
 
@@ -39,16 +37,14 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import tcpseg_bench as TS  # noqa: E402
+import sg_harness as SG  # noqa: E402
 from picotcp_amd import batch  # noqa: E402
-
-H, MTU, HBM_PEAK = TS.H, TS.MTU, TS.HBM_PEAK
+from tcpseg_bench import H, MTU, make_set as make_stream_set  # noqa: E402  (the sets are the segmentation tool's)
 
 
 def make_set(n, P, per, stride, dev, seed):
     """tools/tcpseg_bench.py's set, segmented and fragmented once, with the arrays of the RX legs."""
-    s = TS.make_set(n, P, per, stride, dev, seed)
+    s = make_stream_set(n, P, per, stride, dev, seed)
     cnt, fcnt = s["cnt"], s["fcnt"]
     s["fout"] = torch.zeros_like(s["out"])                                  # the fragments (the reassembly's input)
     batch.tcp_segment_batch(s["buf"], s["sd"], s["grp"], s["n_seg"], s["out"], s["od"], stride, out_seg=s["of"], results=s["res"])
@@ -61,7 +57,7 @@ def make_set(n, P, per, stride, dev, seed):
     s["RP"], s["DP"] = RP, DP
     s["rbuf"] = torch.zeros(n * RP + 16, dtype=torch.uint8, device=dev)
     s["rod"] = batch.desc_to_device(batch.make_desc(np.arange(n, dtype=np.int64) * RP, np.full(n, P)), dev)
-    seq0 = (np.arange(n, dtype=np.uint32) * 2654435761).astype(np.uint32)   # the templates' seq (TS.make_set)
+    seq0 = (np.arange(n, dtype=np.uint32) * 2654435761).astype(np.uint32)   # the templates' seq (make_stream_set)
     s["conn"] = torch.from_numpy(np.stack([seq0, np.zeros(n, np.uint32)], axis=1).reshape(-1).view(np.int32)).to(dev)
     s["rres"] = (torch.empty(n, dtype=torch.uint8, device=dev), torch.empty(n, dtype=torch.int32, device=dev),
                  torch.empty(n * cnt, dtype=torch.uint8, device=dev))
@@ -132,30 +128,7 @@ def run_shape(name, n, P, a, dev, lib):
     legs = {"coalesce": coalesce, "reassemble": reassemble, "segment": segment}
     if lib is not None:
         legs.update({"bare_gather_4waves": bare(2), "bare_gather_flat": bare(3), "seq_copy": seq})
-    graphs = {}
-    for nm, f in legs.items():
-        gph = torch.cuda.CUDAGraph()
-        cs = torch.cuda.Stream(dev)
-        cs.wait_stream(stream)
-        with torch.cuda.stream(cs):
-            with torch.cuda.graph(gph, stream=cs):
-                for s in sets:
-                    f(s, cs)
-        stream.wait_stream(cs)
-        graphs[nm] = gph
-    for _ in range(a.warmup):
-        for gph in graphs.values():
-            gph.replay()
-    torch.cuda.synchronize(dev)
-    times = {nm: [] for nm in legs}
-    for _ in range(a.replays):                               # the legs alternate, replay by replay
-        for nm, gph in graphs.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(stream)
-            gph.replay()
-            e1.record(stream)
-            torch.cuda.synchronize(dev)
-            times[nm].append(e0.elapsed_time(e1) * 1e3 / a.rotate)
+    times = SG.time_legs(legs, sets, dev, stream, a.warmup, a.replays, a.rotate)
     for s in sets:                                           # the timed replays worked on good data (the bare
         coalesce(s, stream)                                  # gather's rounded stores last wrote the regions)
         torch.cuda.synchronize(dev)
@@ -169,14 +142,7 @@ def run_shape(name, n, P, a, dev, lib):
     r = {"shape": name.replace("tcpseg", "tcprx"), "connections": n, "payload_bytes_per_connection": P, "per": per,
          "seg_stride": stride, "segments": cnt, "fragments_of_the_reassemble_leg": fcnt, "rotate": a.rotate,
          "replays": a.replays, "payload_bytes": payload, "outputs_verified_before_and_after_timing": True}
-    for nm, v in times.items():
-        us = float(np.median(v))
-        r[nm + "_us"] = round(us, 2)
-        r[nm + "_us_min_max"] = [round(min(v), 2), round(max(v), 2)]
-        b = moved.get(nm, 2 * payload)
-        r[nm + "_algorithmic_bytes"] = b
-        r[nm + "_TBs"] = round(b / us / 1e6, 3)
-        r[nm + "_fraction_of_8TBs"] = round(b / (us * 1e-6) / HBM_PEAK, 3)
+    SG.summarise(r, times, moved, payload, bytes_key=True)
     r["coalesce_over_reassemble"] = round(r["coalesce_us"] / r["reassemble_us"], 3)
     r["coalesce_over_segment"] = round(r["coalesce_us"] / r["segment_us"], 3)
     if lib is not None:
@@ -185,56 +151,9 @@ def run_shape(name, n, P, a, dev, lib):
         r["coalesce_over_seq_copy"] = round(r["coalesce_us"] / r["seq_copy_us"], 3)
         r["ceiling_store_path"] = "non-temporal whole-unit stores; the coalesce leg uses cached stores, to the byte"
     else:
-        r["ceiling_legs"] = "not measured: tools/bin/libgather_ceiling.so is not built"
+        r["ceiling_legs"] = SG.CEILING_NOT_MEASURED
     return r
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--shape", default="both", choices=["c3", "9000", "both"])
-    ap.add_argument("--n", type=int, default=0, help="connections (0: 4096 x 64512 B, or as many 9000 B ones for the same bytes)")
-    ap.add_argument("--per", type=int, default=1448)
-    ap.add_argument("--stride", type=int, default=1504)
-    ap.add_argument("--rotate", type=int, default=3)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--replays", type=int, default=24)
-    ap.add_argument("--out", default="")
-    a = ap.parse_args()
-    if a.replays < 20:
-        raise SystemExit("--replays: at least 20")
-    if not torch.cuda.is_available():
-        raise SystemExit("tcprx_bench.py measures on the GPU: no HIP device here (not measured)")
-    dev = torch.device("cuda:0")
-    lib = None
-    p = os.path.join(ROOT, "tools", "bin", "libgather_ceiling.so")
-    if os.path.exists(p):
-        lib = ctypes.CDLL(p)
-        lib.seq_copy_launch.restype = ctypes.c_int
-        lib.seq_copy_launch.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
-                                        ctypes.c_uint64, ctypes.c_void_p]
-        lib.gather_ceiling_launch.restype = ctypes.c_int
-        lib.gather_ceiling_launch.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64] + [ctypes.c_void_p] * 4 + \
-            [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
-    else:
-        print(f"tcprx_bench.py: {os.path.relpath(p, ROOT)} is not built (__graft_entry__.build() builds it): the bare "
-              "gather and seq_copy legs and their ratios are NOT measured in this run", file=sys.stderr, flush=True)
-    shapes = []
-    if a.shape in ("c3", "both"):
-        shapes.append(("tcpseg_64512", a.n or 4096, 64512))
-    if a.shape in ("9000", "both"):
-        shapes.append(("tcpseg_9000", a.n or 4096 * 64512 // 9000, 9000))
-    results = []
-    for name, n, P in shapes:
-        r = run_shape(name, n, P, a, dev, lib)
-        print(json.dumps(r), flush=True)
-        results.append(r)
-        torch.cuda.empty_cache()
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump({"device": torch.cuda.get_device_name(0), "results": results}, f, indent=1)
-            f.write("\n")
-
-
 if __name__ == "__main__":
-    main()
+    SG.main("tcprx_bench.py", "connections", (("--per", 1448),), ("tcpseg_64512", "tcpseg_9000"), run_shape)

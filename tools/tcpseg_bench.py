@@ -27,9 +27,7 @@ ACCEPT with both checksums verifying (0) in the IPv4 RX batch.
 """
 from __future__ import annotations
 
-import argparse
 import ctypes
-import json
 import os
 import sys
 
@@ -38,9 +36,9 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+import sg_harness as SG  # noqa: E402
 from picotcp_amd import batch, synth  # noqa: E402
 
-HBM_PEAK = 8.0e12       # MI355X HBM3E, bytes / s (datasheet)
 H = 52                  # 20 + a 32-byte TCP header (timestamp option, padded)
 MTU = 1500
 
@@ -132,30 +130,7 @@ def run_shape(name, n, P, a, dev, lib):
     legs = {"segment": segment, "fragment": fragment}
     if lib is not None:
         legs.update({"bare_scatter_4waves": bare(2), "bare_scatter_flat": bare(3), "seq_copy": seq})
-    graphs = {}
-    for nm, f in legs.items():
-        gph = torch.cuda.CUDAGraph()
-        cs = torch.cuda.Stream(dev)
-        cs.wait_stream(stream)
-        with torch.cuda.stream(cs):
-            with torch.cuda.graph(gph, stream=cs):
-                for s in sets:
-                    f(s, cs)
-        stream.wait_stream(cs)
-        graphs[nm] = gph
-    for _ in range(a.warmup):
-        for gph in graphs.values():
-            gph.replay()
-    torch.cuda.synchronize(dev)
-    times = {nm: [] for nm in legs}
-    for _ in range(a.replays):                               # the legs alternate, replay by replay
-        for nm, gph in graphs.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(stream)
-            gph.replay()
-            e1.record(stream)
-            torch.cuda.synchronize(dev)
-            times[nm].append(e0.elapsed_time(e1) * 1e3 / a.rotate)
+    times = SG.time_legs(legs, sets, dev, stream, a.warmup, a.replays, a.rotate)
     for s in sets:                                           # the timed replays worked on good data
         if not bool((s["res"][0] == batch.V_ACCEPT).all() and (s["fres"][0] == batch.V_ACCEPT).all()):
             raise SystemExit(f"{name}: a timed replay did not accept every stream")
@@ -168,13 +143,7 @@ def run_shape(name, n, P, a, dev, lib):
          "working_set_bytes_per_set": int(sets[0]["buf"].numel() + sets[0]["out"].numel()), "payload_bytes": payload,
          "algorithmic_bytes_segment": moved["segment"], "algorithmic_bytes_fragment": moved["fragment"],
          "segments_verified_in_rx_batch": ok}
-    for nm, v in times.items():
-        us = float(np.median(v))
-        r[nm + "_us"] = round(us, 2)
-        r[nm + "_us_min_max"] = [round(min(v), 2), round(max(v), 2)]
-        b = moved.get(nm, 2 * payload)
-        r[nm + "_TBs"] = round(b / us / 1e6, 3)
-        r[nm + "_fraction_of_8TBs"] = round(b / (us * 1e-6) / HBM_PEAK, 3)
+    SG.summarise(r, times, moved, payload)
     r["segment_over_fragment"] = round(r["segment_us"] / r["fragment_us"], 3)
     if lib is not None:
         r["segment_over_bare_scatter_4waves"] = round(r["segment_us"] / r["bare_scatter_4waves_us"], 3)
@@ -184,56 +153,9 @@ def run_shape(name, n, P, a, dev, lib):
         # and fragment kernels store through the cache, to the byte: these ratios cross two store paths
         r["ceiling_store_path"] = "non-temporal whole-unit stores; segment and fragment legs use cached stores"
     else:
-        r["ceiling_legs"] = "not measured: tools/bin/libgather_ceiling.so is not built"
+        r["ceiling_legs"] = SG.CEILING_NOT_MEASURED
     return r
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--shape", default="both", choices=["c3", "9000", "both"])
-    ap.add_argument("--n", type=int, default=0, help="streams (0: 4096 x 64512 B, or as many 9000 B ones for the same bytes)")
-    ap.add_argument("--per", type=int, default=1448)
-    ap.add_argument("--stride", type=int, default=1504)
-    ap.add_argument("--rotate", type=int, default=3)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--replays", type=int, default=24)
-    ap.add_argument("--out", default="")
-    a = ap.parse_args()
-    if a.replays < 20:
-        raise SystemExit("--replays: at least 20")
-    if not torch.cuda.is_available():
-        raise SystemExit("tcpseg_bench.py measures on the GPU: no HIP device here (not measured)")
-    dev = torch.device("cuda:0")
-    lib = None
-    p = os.path.join(ROOT, "tools", "bin", "libgather_ceiling.so")
-    if os.path.exists(p):
-        lib = ctypes.CDLL(p)
-        lib.seq_copy_launch.restype = ctypes.c_int
-        lib.seq_copy_launch.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
-                                        ctypes.c_uint64, ctypes.c_void_p]
-        lib.gather_ceiling_launch.restype = ctypes.c_int
-        lib.gather_ceiling_launch.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64] + [ctypes.c_void_p] * 4 + \
-            [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
-    else:
-        print(f"tcpseg_bench.py: {os.path.relpath(p, ROOT)} is not built (__graft_entry__.build() builds it): the bare "
-              "scatter and seq_copy legs and their ratios are NOT measured in this run", file=sys.stderr, flush=True)
-    shapes = []
-    if a.shape in ("c3", "both"):
-        shapes.append(("tcpseg_64512", a.n or 4096, 64512))
-    if a.shape in ("9000", "both"):
-        shapes.append(("tcpseg_9000", a.n or 4096 * 64512 // 9000, 9000))
-    results = []
-    for name, n, P in shapes:
-        r = run_shape(name, n, P, a, dev, lib)
-        print(json.dumps(r), flush=True)
-        results.append(r)
-        torch.cuda.empty_cache()
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump({"device": torch.cuda.get_device_name(0), "results": results}, f, indent=1)
-            f.write("\n")
-
-
 if __name__ == "__main__":
-    main()
+    SG.main("tcpseg_bench.py", "streams", (("--per", 1448),), ("tcpseg_64512", "tcpseg_9000"), run_shape)
