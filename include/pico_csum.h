@@ -56,7 +56,9 @@ extern "C" {
  *   4 (added, no bump): pico_ipv4_fragment_batch_dev -- a new entry point breaks no caller;
  *   4 (added, no bump): pico_tcp_segment_batch_dev -- likewise;
  *   4 (added, no bump): pico_tcp_coalesce_batch_dev and its three verdict values, which no other batch
- *      returns -- likewise. */
+ *      returns -- likewise;
+ *   4 (added, no bump): pico_flow_group_batch_dev, pico_flow_group_scratch_bytes, struct pico_csum_flow_key
+ *      and the PICO_CSUM_FLOW_* modes -- likewise. */
 #define PICO_CSUM_ABI_VERSION 4
 
 /* picoTCP pico_err values used here (include/pico_protocol.h:27,31,38 + ENODEV) */
@@ -329,7 +331,8 @@ int pico_ipv4_nat_batch_dev(void *d_base, uint64_t base_len, const struct pico_c
  *   d_frag[]   fragments as pico_ipv4_process_in hands them on (desc.off -> the fragment's
  *              IPv4 header, desc.len = bytes available; header already checked)
  *   d_groups[] 2 uint32 per datagram: first fragment, count -- the fragments one reassembly
- *              tree collects (src / dst / id matched by the stack), in arrival order
+ *              tree collects (src / dst / id matched by pico_flow_group_batch_dev, or by the stack), in
+ *              arrival order
  *   d_out_desc[] per datagram: output region in d_out (off a multiple of 4, len = capacity;
  *              off = 12 mod 16 puts the transport on a 16-byte line: whole-line stores)
  * Tree order by fragment offset ((frag & 0x1FFF) << 3; a repeated offset keeps the earlier
@@ -506,8 +509,9 @@ int pico_tcp_segment_batch_dev(const void *d_base, uint64_t base_len, const stru
  *              there (nothing past it or past base_len is read, with the whole-16-byte-block read rule
  *              above), desc.seed = 0.  The version nibble selects the family: IPv4 (any IHL >= 5, proto
  *              6) or IPv6 with nxthdr 6 and no extension header.
- *   d_groups[] 2 uint32 per connection: first segment, count, IN ARRIVAL ORDER (the host has matched the
- *              4-tuple: the socket lookup is control plane, as NAT's tuple table is)
+ *   d_groups[] 2 uint32 per connection: first segment, count, IN ARRIVAL ORDER (pico_flow_group_batch_dev
+ *              matches the 4-tuple on the device, against the host's connection table; a host that has
+ *              matched it itself passes its own groups)
  *   d_conn[]   2 uint32 per connection: rcv_nxt, cflags.  cflags bit 0 = the connection's sack_ok; the
  *              other bits are reserved and must be 0.
  *   d_out_desc[] per connection: output region in d_out (off any alignment -- off = 0 mod 16: whole-line
@@ -563,6 +567,81 @@ int pico_tcp_coalesce_batch_dev(const void *d_base, uint64_t base_len, const str
                                 void *d_out, uint64_t out_len, const struct pico_csum_desc *d_out_desc,
                                 uint32_t *d_out_len, uint8_t *d_seg_verdict, uint8_t *d_verdict, uint32_t flags,
                                 void *stream);
+
+/* Flow grouping: a verified burst, in arrival order, becomes the inputs of the three gather batches above
+ * -- each flow's frames contiguous, in arrival order, and the groups[] over them -- on the device, with no
+ * host pass per frame.  The batch form of the reference's per-frame lookups: pico_socket_tcp_deliver
+ * (modules/pico_socket_tcp.c:125-226) walks the port's sockets comparing remote port, remote address and
+ * local address; the fragment code compares id, source and destination (modules/pico_fragments.c:104-122,
+ * :160-178, :447, :523).  A grouping by key equality: a parse, a hash table and a stable sort.
+ *   d_desc[]   one frame each: desc.off -> the network header, desc.len = bytes available from there; with
+ *              PICO_CSUM_FLOW_F_ETH desc.off -> the Ethernet header and the network header is 14 bytes on
+ *              (the Ethernet batch's descriptors as they are).  desc.seed is not read.
+ *   d_verdict_in  NULL, or the verdict array the Ethernet / IPv4 / IPv6 RX batch wrote for these frames
+ *   mode_flags one of PICO_CSUM_FLOW_TCP / _FRAG4 / _FRAG6, | PICO_CSUM_FLOW_F_ETH
+ * Selection.  A frame takes part when its region lies inside base_len (with F_ETH: and holds the 14
+ * bytes), when, with d_verdict_in, its verdict with V_IPV6 masked off is V_ACCEPT (TCP mode) or V_FRAG
+ * (the FRAG modes), and when it parses:
+ *   TCP    IPv4: version 4, IHL >= 5, proto 6, neither MF nor an offset, the 4 port bytes at 4 IHL inside
+ *          desc.len; IPv6: version 6, nxthdr 6 directly behind the fixed header (what the coalescing batch
+ *          accepts), 44 bytes inside desc.len.  Key: family, src, dst, sport, dport.
+ *   FRAG4  version 4, IHL >= 5, 20 bytes inside desc.len, MF or an offset.  Key: src, dst, id (bytes 4-5).
+ *   FRAG6  version 6 and the extension-header walk of pico_ipv6_reassemble_batch_dev reaches the transport
+ *          behind a fragment header whose 8 bytes lie inside desc.len.  Key: src, dst, that header's
+ *          32-bit id.
+ * Nothing past desc.len or base_len contributes; reads follow the whole-16-byte-block rule above.
+ * Groups.  Two selected frames are in one group exactly when their keys are equal.  In TCP mode the first
+ * n_known groups are the host's connection table: group t < n_known is d_known[t]'s (compared field by
+ * field: family, all 16 bytes of src and of dst, sport, dport; reserved is not compared), possibly empty;
+ * a table key equal to an earlier one gets an empty group.  Groups of keys not in the table follow in order
+ * of their first arrival.  n_known must be 0 in the FRAG modes.  Members of a group are in arrival order
+ * (ascending input index).
+ *   d_out_groups[2g], [2g+1]  the group's first slot and count (uint32[2 (n + n_known)]); an empty table
+ *              group and every entry from n_groups up to n + n_known are {0, 0}
+ *   d_out_desc[slot]   {network header offset, bytes available from there, 0}: with F_ETH {off + 14,
+ *              len - 14, 0}, else {off, len, 0}
+ *   d_out_index[slot]  the frame's input index.  Slots past the selected frames hold {0, 0, 0} and the
+ *              unselected input indexes in ascending order: d_out_index is a permutation of 0 .. n-1
+ *   d_out_counts[0]    n_groups (the n_known table groups included);  [1] the number of selected frames
+ * d_out_desc and d_out_groups go to pico_ipv4_reassemble_batch_dev, pico_ipv6_reassemble_batch_dev and
+ * pico_tcp_coalesce_batch_dev as they are (n_frag / n_seg = n; n_dgram / n_conn = n_groups, or a fixed cap:
+ * a padded or empty group is those batches' "empty group" -- MALFORMED, nothing written).  Table groups
+ * keep table order, so the host's per-connection d_conn[] / d_out_desc[] line up with no round trip; the
+ * host reads back only d_out_counts and, for the groups >= n_known, d_out_index[first]: that leader's
+ * frame holds the new flow's tuple.
+ * One documented difference: the reference matches a socket bound to INADDR_ANY against any destination;
+ * the batch groups by exact destination.  Two groups that resolve to one socket are the host's to merge.
+ * Errors, all checked on the host before any launch, -EINVAL: n == 0 or n + n_known > 0x00FFFFFF; an
+ * unknown mode or flag; n_known != 0 in a FRAG mode; d_known == NULL with n_known != 0; a NULL d_base,
+ * d_desc, d_out_desc, d_out_index, d_out_groups, d_out_counts or d_scratch; d_desc, d_out_desc or d_scratch
+ * not 16-byte aligned; scratch_len < pico_flow_group_scratch_bytes(n, n_known) (pure host arithmetic; 0 =
+ * out of range; never smaller for a larger n or n_known).  No usable device: -ENODEV.
+ * Results never depend on hash_seed (it exists so that a host can make hash collisions unpredictable to a
+ * sender, as an RSS key does), on the scratch contents on entry, or on the launch shape.  Everything runs
+ * on `stream`: no allocation, no host synchronisation, no library scratch -- the caller's d_scratch holds
+ * everything, and the batch initialises on the stream what it needs of it.  The number of launches
+ * depends only on n and n_known, so a call is capturable into a graph as a straight line, together with
+ * the gather batch behind it.  Every device loop is bounded by a value known on entry and no lane waits
+ * for another lane's store. */
+struct pico_csum_flow_key {      /* 40 bytes */
+    uint8_t  src[16];            /* the frame's source address as stored; IPv4: bytes 0-3, rest 0 */
+    uint8_t  dst[16];            /* the frame's destination address, likewise */
+    uint16_t sport, dport;       /* TCP ports as stored (network byte order) */
+    uint8_t  family;             /* 4 or 6 */
+    uint8_t  reserved[3];        /* 0 */
+};
+#define PICO_CSUM_FLOW_TCP   1u  /* key: family, src, dst, sport, dport */
+#define PICO_CSUM_FLOW_FRAG4 2u  /* key: src, dst, id (header bytes 4-5) */
+#define PICO_CSUM_FLOW_FRAG6 3u  /* key: src, dst, the fragment header's 32-bit id */
+#define PICO_CSUM_FLOW_F_ETH 0x10u /* desc.off -> the Ethernet header; the network header is 14 bytes on */
+
+uint64_t pico_flow_group_scratch_bytes(uint32_t n, uint32_t n_known);   /* pure host arithmetic; 0 = out of range */
+
+int pico_flow_group_batch_dev(const void *d_base, uint64_t base_len, const struct pico_csum_desc *d_desc, uint32_t n,
+                              const uint8_t *d_verdict_in, uint32_t mode_flags,
+                              const struct pico_csum_flow_key *d_known, uint32_t n_known, uint32_t hash_seed,
+                              struct pico_csum_desc *d_out_desc, uint32_t *d_out_index, uint32_t *d_out_groups,
+                              uint32_t *d_out_counts, void *d_scratch, uint64_t scratch_len, void *stream);
 
 /* ---------------------------------------------------------------- layer 3 */
 

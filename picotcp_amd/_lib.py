@@ -35,6 +35,8 @@ EXPORTED = (
     "pico_ipv4_fragment_batch_dev",
     "pico_tcp_segment_batch_dev",
     "pico_tcp_coalesce_batch_dev",
+    "pico_flow_group_scratch_bytes",
+    "pico_flow_group_batch_dev",
     "pico_csum_ctx_create",
     "pico_csum_ctx_destroy",
     "pico_checksum_batch_uniform_host",
@@ -64,6 +66,7 @@ V_DROP_L2, V_ARP, V_IPV6 = 32, 64, 128
 V_UNTOUCHED = 32            # NAT batch (same bit as V_DROP_L2)
 V_LOCAL_SRC, V_DUPLICATE = 32, 64   # forwarding batch (same bits as V_DROP_L2 / V_ARP)
 V_TCP_CTRL, V_TCP_OLD, V_TCP_HELD = 32, 64, 128   # TCP coalescing batch (same bits as V_DROP_L2 / V_ARP / V_IPV6)
+FLOW_TCP, FLOW_FRAG4, FLOW_FRAG6, FLOW_F_ETH = 1, 2, 3, 0x10   # pico_flow_group_batch_dev's mode_flags
 EINVAL, ENODEV, EIO, ENOMEM = 22, 19, 5, 12
 
 
@@ -112,6 +115,9 @@ def load() -> ctypes.CDLL:
     sig("pico_ipv4_fragment_batch_dev", ctypes.c_int, vp, u64, vp, u32, u32, vp, u32, vp, u64, vp, u32, vp, vp, vp, vp, u32, vp)
     sig("pico_tcp_segment_batch_dev", ctypes.c_int, vp, u64, vp, u32, vp, u32, vp, u64, vp, u32, vp, vp, vp, u32, vp)
     sig("pico_tcp_coalesce_batch_dev", ctypes.c_int, vp, u64, vp, u32, vp, vp, u32, vp, u64, vp, vp, vp, vp, u32, vp)
+    if hasattr(lib, "pico_flow_group_batch_dev"):        # (an A/B build of an older round lacks it)
+        sig("pico_flow_group_scratch_bytes", u64, u32, u32)
+        sig("pico_flow_group_batch_dev", ctypes.c_int, vp, u64, vp, u32, vp, u32, vp, u32, u32, vp, vp, vp, vp, vp, u64, vp)
     sig("pico_csum_ctx_create", vp, ctypes.c_int, u64)
     sig("pico_csum_ctx_destroy", None, vp)
     sig("pico_checksum_batch_uniform_host", ctypes.c_int, vp, vp, u64, u32, u32, u32, vp)

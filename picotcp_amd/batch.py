@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (F_NXTHDR_DISPATCH, F_TX, F_WRITE, V_ACCEPT, V_ARP, V_DROP_L2, V_DUPLICATE,  # noqa: F401
+from ._lib import (F_NXTHDR_DISPATCH, F_TX, F_WRITE, FLOW_F_ETH, FLOW_FRAG4, FLOW_FRAG6, FLOW_TCP, V_ACCEPT, V_ARP, V_DROP_L2, V_DUPLICATE,  # noqa: F401
                    V_EXPIRED, V_FRAG, V_IPV6, V_L4_BAD, V_LOCAL_SRC, V_MALFORMED, V_NET_BAD, V_TCP_CTRL, V_TCP_HELD,
                    V_TCP_OLD, V_UNTOUCHED)
 
@@ -433,6 +433,67 @@ def tcp_coalesce_batch(base: torch.Tensor, seg_desc: torch.Tensor, n_seg: int, g
                                                _ptr(out), out.numel(), _ptr(out_desc), _ptr(ol), _ptr(sv), _ptr(v), flags,
                                                _stream_handle(stream)))
     return v, ol, sv
+
+
+# struct pico_csum_flow_key (include/pico_csum.h): one entry of the flow grouping's connection table
+FLOW_KEY_DTYPE = np.dtype([("src", "u1", 16), ("dst", "u1", 16), ("sport", "<u2"), ("dport", "<u2"), ("family", "u1"),
+                           ("reserved", "u1", 3)])
+assert FLOW_KEY_DTYPE.itemsize == 40
+_FLOW_OUTS = (("out_desc", torch.uint8, 1, False), ("out_index", torch.int32, 4, False), ("out_groups", torch.int32, 4, False),
+              ("out_counts", torch.int32, 4, False))
+
+
+def flow_group_scratch_bytes(n: int, n_known: int = 0) -> int:
+    """pico_flow_group_scratch_bytes: the scratch a grouping of n frames against n_known table keys needs
+    (host arithmetic; 0 = out of range)."""
+    if not (0 <= n <= 0xFFFFFFFF and 0 <= n_known <= 0xFFFFFFFF):
+        return 0
+    return int(_lib.load().pico_flow_group_scratch_bytes(n, n_known))
+
+
+def flow_group_batch(base: torch.Tensor, desc: torch.Tensor, n: int, mode_flags: int, verdict_in: torch.Tensor | None = None,
+                     known: torch.Tensor | None = None, n_known: int = 0, hash_seed: int = 0,
+                     scratch: torch.Tensor | None = None, stream=None, results=None):
+    """Flow grouping (pico_flow_group_batch_dev; the batch form of pico_socket_tcp_deliver's and the
+    fragment trees' key comparisons): the n frames of a verified burst, in arrival order, become the
+    group-contiguous descriptors and the (first, count) groups that ipv4_reassemble_batch,
+    ipv6_reassemble_batch and tcp_coalesce_batch take.  mode_flags = FLOW_TCP / FLOW_FRAG4 / FLOW_FRAG6,
+    | FLOW_F_ETH when desc.off -> the Ethernet header; verdict_in = the RX batch's verdicts (uint8[n]) or
+    None; known = the connection table (uint8 tensor of 40 * n_known bytes, FLOW_KEY_DTYPE; TCP mode),
+    whose keys own groups 0 .. n_known-1; scratch = a uint8 tensor of flow_group_scratch_bytes(n, n_known)
+    bytes (None allocates one).  Returns (out_desc uint8[16 n], out_index int32[n], out_groups
+    int32[2 (n + n_known)], out_counts int32[2] = n_groups, selected frames); `results` may pass that
+    quadruple preallocated."""
+    tensors = dict(desc=desc)
+    for name, t in (("verdict_in", verdict_in), ("known", known), ("scratch", scratch)):
+        if t is not None:
+            tensors[name] = t
+    dev = _on_batch_device(base, **tensors)
+    _require_u8(base, "base")
+    if n <= 0 or n_known < 0:
+        raise ValueError(f"n = {n}, n_known = {n_known}: at least one frame")
+    need = flow_group_scratch_bytes(n, n_known)
+    if need == 0:
+        raise ValueError(f"n + n_known = {n + n_known} is out of range (at most 0x00FFFFFF)")
+    _desc_bytes(desc, n, "desc")
+    if verdict_in is not None:
+        _check_out(verdict_in, n, "verdict_in", dev, 1)
+    if n_known:
+        if known is None or not known.is_contiguous() or known.numel() * known.element_size() < 40 * n_known:
+            raise ValueError(f"known must be a contiguous tensor of {n_known} 40-byte keys")
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    _require_u8(scratch, "scratch")
+    if scratch.numel() < need:
+        raise ValueError(f"scratch holds {scratch.numel()} bytes, the batch needs {need}")
+    od, oi, og, oc = _results(results, _FLOW_OUTS, (16 * n, n, 2 * (n + n_known), 2), dev)
+    lib = _lib.load()
+    _lib.check("pico_flow_group_batch_dev",
+               lib.pico_flow_group_batch_dev(_ptr(base), base.numel(), _ptr(desc), n, _ptr(verdict_in), mode_flags,
+                                             _ptr(known) if n_known else None, n_known, hash_seed & 0xFFFFFFFF, _ptr(od),
+                                             _ptr(oi), _ptr(og), _ptr(oc), _ptr(scratch), scratch.numel(),
+                                             _stream_handle(stream)))
+    return od, oi, og, oc
 
 
 STREAM_OFF = 0xFF

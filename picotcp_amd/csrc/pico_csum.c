@@ -57,6 +57,11 @@ int pico_csum_launch_tcp_coalesce(const void *base, uint64_t base_len, const voi
                                   const uint32_t *groups, const uint32_t *conn, uint32_t n_conn, void *out,
                                   uint64_t out_len, const void *out_desc, uint32_t *o_len, uint8_t *seg_verdict,
                                   uint8_t *verdict, void *stream);
+int pico_csum_launch_flow_group(const void *base, uint64_t base_len, const void *desc, uint32_t n,
+                                const uint8_t *verdict_in, uint32_t mode_flags, const void *known, uint32_t n_known,
+                                uint32_t seed, void *o_desc, uint32_t *o_index, uint32_t *o_groups, uint32_t *o_counts,
+                                void *scratch, const uint64_t *lay, uint32_t cap, uint32_t ntiles, uint32_t passes,
+                                void *stream);
 
 /* ------------------------------------------------------------------ errors */
 
@@ -687,6 +692,83 @@ int pico_tcp_coalesce_batch_dev(const void *d_base, uint64_t base_len, const str
                                                        out_len, d_out_desc, d_out_len, d_seg_verdict, d_verdict,
                                                        stream),
                          "pico_tcp_coalesce_batch_dev");
+}
+
+/* The flow grouping's scratch, section by section (each a multiple of 16 bytes): lay[0..6] = the byte
+ * offsets of the entries' keys (48 bytes each), the open-addressed table (cap slots: the power of two
+ * >= 2 (n + n_known)), the sort's two (key, value) buffer pairs and the digit counts (256 per tile of
+ * 1024 frames); lay[7] = the total.  passes = 8-bit digits over the ceil(log2(n + n_known + 1)) key bits.
+ * 0: out of range. */
+#define FLOW_MAX_ENTRIES 0x00FFFFFFu
+#define FLOW_TILE 1024u
+static uint64_t flow_layout(uint32_t n, uint32_t n_known, uint64_t lay[8], uint32_t *cap, uint32_t *ntiles,
+                            uint32_t *passes)
+{
+    uint64_t N = (uint64_t)n + n_known, c = 4, pos = 0, col;     /* (4 slots: a 16-byte section) */
+    uint32_t bits = 1, t;
+    if (n == 0 || N > FLOW_MAX_ENTRIES)
+        return 0;
+    while (c < 2 * N)
+        c <<= 1;
+    while ((1ull << bits) < N + 1)
+        ++bits;
+    t = (uint32_t)(((uint64_t)n + FLOW_TILE - 1) / FLOW_TILE);
+    col = (4ull * n + 15u) & ~15ull;
+    lay[0] = pos, pos += 48ull * N;
+    lay[1] = pos, pos += 4ull * c;
+    lay[2] = pos, pos += col;
+    lay[3] = pos, pos += col;
+    lay[4] = pos, pos += col;
+    lay[5] = pos, pos += col;
+    lay[6] = pos, pos += (4ull * 256u * t + 15u) & ~15ull;
+    lay[7] = pos;
+    *cap = (uint32_t)c;
+    *ntiles = t;
+    *passes = (bits + 7u) / 8u;
+    return pos;
+}
+
+uint64_t pico_flow_group_scratch_bytes(uint32_t n, uint32_t n_known)
+{
+    uint64_t lay[8];
+    uint32_t cap, ntiles, passes;
+    return flow_layout(n, n_known, lay, &cap, &ntiles, &passes);
+}
+
+int pico_flow_group_batch_dev(const void *d_base, uint64_t base_len, const struct pico_csum_desc *d_desc, uint32_t n,
+                              const uint8_t *d_verdict_in, uint32_t mode_flags,
+                              const struct pico_csum_flow_key *d_known, uint32_t n_known, uint32_t hash_seed,
+                              struct pico_csum_desc *d_out_desc, uint32_t *d_out_index, uint32_t *d_out_groups,
+                              uint32_t *d_out_counts, void *d_scratch, uint64_t scratch_len, void *stream)
+{
+    int rc;
+    uint64_t lay[8], need;
+    uint32_t cap, ntiles, passes;
+    const uint32_t mode = mode_flags & ~PICO_CSUM_FLOW_F_ETH;
+    if (n == 0 || (uint64_t)n + n_known > FLOW_MAX_ENTRIES)
+        return fail(PICO_CSUM_EINVAL, "n %u, n_known %u: 1 <= n, n + n_known <= 0x%x", n, n_known, FLOW_MAX_ENTRIES);
+    if (mode != PICO_CSUM_FLOW_TCP && mode != PICO_CSUM_FLOW_FRAG4 && mode != PICO_CSUM_FLOW_FRAG6)
+        return fail(PICO_CSUM_EINVAL, "unknown mode or flag 0x%x (PICO_CSUM_FLOW_TCP / _FRAG4 / _FRAG6, | _F_ETH)", mode_flags);
+    if (mode != PICO_CSUM_FLOW_TCP && n_known != 0)
+        return fail(PICO_CSUM_EINVAL, "n_known %u: the connection table belongs to PICO_CSUM_FLOW_TCP", n_known);
+    if (n_known != 0 && !d_known)
+        return fail(PICO_CSUM_EINVAL, "d_known is NULL with n_known %u", n_known);
+    if (!d_base || !d_desc || !d_out_desc || !d_out_index || !d_out_groups || !d_out_counts || !d_scratch)
+        return fail(PICO_CSUM_EINVAL, "NULL buffer");
+    if (((uintptr_t)d_desc & 15u) != 0 || ((uintptr_t)d_out_desc & 15u) != 0 || ((uintptr_t)d_scratch & 15u) != 0)
+        return fail(PICO_CSUM_EINVAL, "descriptor arrays and d_scratch must be 16-byte aligned");
+    if (((uintptr_t)d_out_index & 3u) != 0 || ((uintptr_t)d_out_groups & 3u) != 0 || ((uintptr_t)d_out_counts & 3u) != 0)
+        return fail(PICO_CSUM_EINVAL, "d_out_index, d_out_groups and d_out_counts must be 4-byte aligned");
+    need = flow_layout(n, n_known, lay, &cap, &ntiles, &passes);
+    if (scratch_len < need)
+        return fail(PICO_CSUM_EINVAL, "scratch_len %llu: pico_flow_group_scratch_bytes(%u, %u) = %llu",
+                    (unsigned long long)scratch_len, n, n_known, (unsigned long long)need);
+    if ((rc = need_device()) != 0)
+        return rc;
+    return launch_status(pico_csum_launch_flow_group(d_base, base_len, d_desc, n, d_verdict_in, mode_flags, d_known,
+                                                     n_known, hash_seed, d_out_desc, d_out_index, d_out_groups,
+                                                     d_out_counts, d_scratch, lay, cap, ntiles, passes, stream),
+                         "pico_flow_group_batch_dev");
 }
 
 /* ------------------------------------------------------------------ layer 3 */

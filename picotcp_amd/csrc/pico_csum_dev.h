@@ -435,7 +435,8 @@ __device__ __noinline__ int walk_dst(const uint8_t* __restrict__ h, uint32_t ava
     } while (0)
 
 // Returns kind + 1 | net_len << 8 | proto << 24 | f->frag << 32 (the last fragment header's
-// offset / M field, :754) -- registers only, no stack slots for outputs.
+// offset / M field, :754) | that fragment header's byte offset in the datagram << 48 (the flow
+// grouping reads its id there) -- registers only, no stack slots for outputs.
 __device__ __forceinline__ uint64_t ipv6_walk_packed(const uint8_t* __restrict__ h,
                                                                            uint32_t avail) {
     const uint32_t plen = ((uint32_t)h[4] << 8) | h[5];
@@ -461,7 +462,7 @@ __device__ __forceinline__ uint64_t ipv6_walk_packed(const uint8_t* __restrict__
     // the walk: f->net_len (uint16) moves by >= 8 bytes a step
     uint32_t net_len = 40u, cur_nexthdr = 6u;
     bool must_align = false, frag = false;
-    uint32_t om = 0;
+    uint32_t om = 0, fo = 0;
     nx = h[6];
     ptr = 40u;
     for (;;) {
@@ -469,7 +470,8 @@ __device__ __forceinline__ uint64_t ipv6_walk_packed(const uint8_t* __restrict__
         uint32_t cur_optlen;
         if (nx == 6u || nx == 17u || nx == 58u) {
             if (must_align && (plen & 7u) != 0u) return (uint64_t)(WALK_DROP + 1);
-            return ((uint64_t)om << 32) | (uint32_t)((frag ? WALK_FRAG : WALK_PROTO) + 1) | (net_len << 8) | (nx << 24);
+            return ((uint64_t)fo << 48) | ((uint64_t)om << 32) | (uint32_t)((frag ? WALK_FRAG : WALK_PROTO) + 1) |
+                   (net_len << 8) | (nx << 24);
         } else if (nx == 0u) {                                      // hop-by-hop: only first
             if (cur_nexthdr != 6u) return (uint64_t)(WALK_DROP + 1);
             WBYTE(e + 1u, b);
@@ -493,6 +495,7 @@ __device__ __forceinline__ uint64_t ipv6_walk_packed(const uint8_t* __restrict__
             WBYTE(e + 3u, om1);
             WBYTE(e + 2u, om0);
             om = (om0 << 8) | om1;
+            fo = e;
             frag = true;
             if ((om1 & 1u) && (plen & 7u) != 0u) return (uint64_t)(WALK_DROP + 1);
         } else if (nx == 60u) {                                     // destination options

@@ -679,3 +679,20 @@ def tcp_rx_bursts(n_conn: int, seed: int = 83, family=4, thl=32, per=1448, max_b
         conns.append((frames, rcv, bool(rng.integers(2)), P))
         streams.append(data)
     return conns, streams
+
+
+def interleave_groups(desc, groups, seed: int = 91):
+    """A seeded merge of group-contiguous frames into one arrival order that keeps each group's own order
+    (what a link delivers when several flows send at once): desc = the frames' descriptors (any array
+    indexed by frame), groups = (first, count) pairs.  Returns (desc[perm], perm): arrival i is input
+    frame perm[i]; frames no group covers are dropped."""
+    groups = np.asarray(groups, dtype=np.int64).reshape(-1, 2)
+    owner = np.repeat(np.arange(groups.shape[0]), groups[:, 1])
+    rng = np.random.default_rng(seed)
+    owner = owner[rng.permutation(owner.size)]              # which group sends at each arrival
+    nxt = groups[:, 0].copy()
+    perm = np.empty(owner.size, np.int64)
+    for i, g in enumerate(owner):
+        perm[i] = nxt[g]
+        nxt[g] += 1
+    return np.asarray(desc)[perm], perm
