@@ -58,7 +58,8 @@ extern "C" {
  *   4 (added, no bump): pico_tcp_coalesce_batch_dev and its three verdict values, which no other batch
  *      returns -- likewise;
  *   4 (added, no bump): pico_flow_group_batch_dev, pico_flow_group_scratch_bytes, struct pico_csum_flow_key
- *      and the PICO_CSUM_FLOW_* modes -- likewise. */
+ *      and the PICO_CSUM_FLOW_* modes -- likewise;
+ *   4 (added, no bump): pico_tcp_ack_batch_dev and struct pico_csum_tcp_ack -- likewise. */
 #define PICO_CSUM_ABI_VERSION 4
 
 /* picoTCP pico_err values used here (include/pico_protocol.h:27,31,38 + ENODEV) */
@@ -567,6 +568,90 @@ int pico_tcp_coalesce_batch_dev(const void *d_base, uint64_t base_len, const str
                                 void *d_out, uint64_t out_len, const struct pico_csum_desc *d_out_desc,
                                 uint32_t *d_out_len, uint8_t *d_seg_verdict, uint8_t *d_verdict, uint32_t flags,
                                 void *stream);
+
+/* The burst's ACKs: one launch behind pico_tcp_coalesce_batch_dev on the same stream, reading the
+ * coalescing's own inputs and outputs.  It finishes the checksum verdicts the coalescing left open and
+ * writes one ready-to-send ACK frame per connection, SACK blocks and both checksums included.  The batch
+ * form of tcp_data_in_send_ack -> tcp_send_ack -> tcp_send_empty (modules/pico_tcp.c:1716-1725, :1324-1327,
+ * :1286-1322) with tcp_sack_prepare (:1597-1657), tcp_options_size (:703-731), tcp_add_options /
+ * tcp_add_sack_option (:582-617, :560-580), tcp_set_space (:681-700) and pico_ipv4_frame_push
+ * (modules/pico_ipv4.c:1039-1079).
+ *   d_base, d_seg, d_groups, d_conn   as the coalescing took them
+ *   d_out_len, d_seg_verdict          as the coalescing wrote them (both required); d_seg_verdict is updated
+ *              in place
+ *   d_tmpl[g]  desc.off -> the connection's header template in d_tmpl_base: a network header followed by a
+ *              20-byte TCP header, desc.len >= N + 20 (nothing past it or past tmpl_len is read).  The family
+ *              rule and its order are pico_tcp_segment_batch_dev's: the version nibble selects IPv4 (IHL 5,
+ *              proto 6; N = 20) or IPv6 (nxthdr 6, no extension header; N = 40).  Taken from it: the addresses,
+ *              tos / flow label, ttl / hop limit, the IPv4 id, the ports, seq (the host's snd_nxt), the low
+ *              nibble of TCP byte 12 (the reference's `jumbo`) and the urgent pointer.  Its own len / frag /
+ *              crc / ack / rwnd / flags / thl are not read.
+ *   d_ack[g]   struct pico_csum_tcp_ack: space = the free receive space BEFORE this burst (tcpq_in.max_size -
+ *              tcpq_in.size), tsval / tsecr in host order, aflags bit 0 = ts_ok (the rest reserved, 0)
+ *   d_out_desc[g]  the frame's region in d_out (off any alignment; len >= the frame: 100 bytes always do)
+ *   flags      reserved: anything but 0 is -EINVAL
+ * Per connection g, with rcv' = rcv_nxt + d_out_len[g]:
+ *   1. Every segment of the group whose verdict is TCP_OLD or TCP_HELD is verified with pico_tcp_checksum,
+ *      with the coalescing's parse and pseudo-header rules (IPv4: pico_tcp_checksum_ipv4; IPv6: always the
+ *      TCP pseudo header) and its read rules; each payload byte is read once and nothing is copied.  One that
+ *      fails becomes L4_BAD in d_seg_verdict.  Every other verdict stays as it is (a segment marked TCP_OLD /
+ *      TCP_HELD that does not parse as a data segment was not marked by the coalescing: it is left alone and
+ *      counts for nothing).
+ *   2. An ACK is due when at least one segment of the group is now ACCEPT, TCP_OLD or TCP_HELD: the segments
+ *      that reach tcp_data_in, each of which draws a tcp_send_ack in the reference.  Otherwise nothing is
+ *      written and d_out_ack[g] = {0, 0, 0} (d_verdict[g] ACCEPT).
+ *   3. The SACK blocks, with sack_ok (cflags bit 0) only -- without it the reference drops a high segment
+ *      (:1696), so held segments contribute nothing.  The queue is the verified TCP_HELD segments, unique by
+ *      seq with the earliest arrival kept (pico_tree_insert refuses the later one), in ascending order of
+ *      seq - rcv' (pico_seq_compare's order: a held segment lies at or beyond rcv').  tcp_sack_prepare is
+ *      applied to that queue and rcv' LITERALLY, with the reference's own first_segment / next_segment
+ *      (:161-179) and its quirks: next_segment is not the tree's successor but the segment that starts
+ *      exactly where this one ends, or none, so the walk follows ONE contiguous run from the queue's lowest
+ *      segment and ends at its first gap -- in practice at most one block, the lowest held run, and later
+ *      runs are never reported; at most 3 blocks, pushed to the front of the list (emitted highest-first);
+ *      the segment that breaks a run closes the open block and is itself skipped; left == 0 means "no open
+ *      block" (a run starting at seq 0 loses its first segment); and `pkt->seq < rcv_nxt` is a raw compare
+ *      (past a 2^32 wrap a held segment's seq is below rcv': skipped).
+ *   4. The window (tcp_set_space): space_after = max(0, space - d_out_len[g] - held), held = the payload bytes
+ *      of the queue (with sack_ok only: the bytes the reference's tcpq_in holds); while space_after > 0xFFFF it
+ *      is halved and shift incremented; rwnd = (uint16)space_after, the WS option carries shift.
+ *   5. The options (flags = ACK): WS (03 03 shift), then timestamps (08 0a tsval tsecr, with ts_ok), then the
+ *      SACK option (05, 2 + 8 b, the blocks) when there are blocks; the area's size is those bytes + 1
+ *      (tcp_options_size counts an END) rounded up to a multiple of 4, the rest NOOP (01) with END (00) as
+ *      the last byte.  thl = 20 + that size: 24 ... 60.
+ *   6. The frame, N + thl bytes at d_out + d_out_desc[g].off: the template with flags = 0x10, ack = rcv',
+ *      rwnd, thl and the options; IPv4 len, frag = 40 00 and crc = pico_ipv4_checksum; the IPv6 payload
+ *      length; the TCP crc with the pseudo header of the template's addresses.  d_out_ack[g] = {that offset,
+ *      N + thl, 0}: with d_out, the input of the TX path or of pico_ipv4_checksum_batch_dev /
+ *      pico_ipv6_checksum_batch_dev as it is.
+ *   d_verdict[g]  ACCEPT, or MALFORMED = nothing of the region is written, d_out_ack[g] = {0, 0, 0} and the
+ *              group's segment verdicts are left as they came: an empty group, one past n_seg or of more than
+ *              512 segments; reserved cflags or aflags; a template past tmpl_len or one that fails the family
+ *              checks; an output region past out_len or smaller than the frame.
+ * No byte outside a region is written, and inside it only the frame's own bytes.  d_out_ack and d_verdict
+ * may each be NULL.  Documented differences from the reference: ONE ACK per connection per burst (the
+ * reference sends one per data segment: INTEGRATION.md 5a-rx); blocks whenever verified held segments exist
+ * (tcp_sack_prepare runs only on a high segment, skips while earlier blocks are pending, and starts at
+ * delivered segments the application has not read yet: the batch's queue holds the held segments only,
+ * the delivered bytes being in the reader's region); tsecr is the
+ * host's (the reference echoes the last parsed segment's tsval); tcp_sack_prepare's quirks are kept, not
+ * repaired.  The host keeps tsecr, the delayed-ACK policy and tcp_ack.
+ * Host checks, -EINVAL before any launch: a NULL required pointer; d_seg, d_tmpl, d_out_desc or d_out_ack not
+ * 16-byte aligned; d_groups, d_conn, d_out_len or d_ack not 4-byte aligned; flags != 0.  n_conn == 0 is a
+ * no-op; without a device -ENODEV.  One launch (the coalescing's two shapes, chosen the same way), no
+ * allocation, no library scratch, no host synchronisation: capturable behind the coalescing as a straight
+ * line.  Results never depend on the launch shape. */
+struct pico_csum_tcp_ack {       /* 16 bytes, per connection, host-filled */
+    uint32_t space;              /* free receive space before this burst */
+    uint32_t tsval, tsecr;       /* host order; written big-endian when ts_ok */
+    uint32_t aflags;             /* bit 0 = ts_ok; the rest reserved, must be 0 */
+};
+int pico_tcp_ack_batch_dev(const void *d_base, uint64_t base_len, const struct pico_csum_desc *d_seg, uint32_t n_seg,
+                           const uint32_t *d_groups, const uint32_t *d_conn, uint32_t n_conn, const uint32_t *d_out_len,
+                           uint8_t *d_seg_verdict, const void *d_tmpl_base, uint64_t tmpl_len,
+                           const struct pico_csum_desc *d_tmpl, const struct pico_csum_tcp_ack *d_ack, void *d_out,
+                           uint64_t out_len, const struct pico_csum_desc *d_out_desc, struct pico_csum_desc *d_out_ack,
+                           uint8_t *d_verdict, uint32_t flags, void *stream);
 
 /* Flow grouping: a verified burst, in arrival order, becomes the inputs of the three gather batches above
  * -- each flow's frames contiguous, in arrival order, and the groups[] over them -- on the device, with no

@@ -35,6 +35,7 @@ EXPORTED = (
     "pico_ipv4_fragment_batch_dev",
     "pico_tcp_segment_batch_dev",
     "pico_tcp_coalesce_batch_dev",
+    "pico_tcp_ack_batch_dev",
     "pico_flow_group_scratch_bytes",
     "pico_flow_group_batch_dev",
     "pico_csum_ctx_create",
@@ -115,6 +116,9 @@ def load() -> ctypes.CDLL:
     sig("pico_ipv4_fragment_batch_dev", ctypes.c_int, vp, u64, vp, u32, u32, vp, u32, vp, u64, vp, u32, vp, vp, vp, vp, u32, vp)
     sig("pico_tcp_segment_batch_dev", ctypes.c_int, vp, u64, vp, u32, vp, u32, vp, u64, vp, u32, vp, vp, vp, u32, vp)
     sig("pico_tcp_coalesce_batch_dev", ctypes.c_int, vp, u64, vp, u32, vp, vp, u32, vp, u64, vp, vp, vp, vp, u32, vp)
+    if hasattr(lib, "pico_tcp_ack_batch_dev"):           # (likewise)
+        sig("pico_tcp_ack_batch_dev", ctypes.c_int, vp, u64, vp, u32, vp, vp, u32, vp, vp, vp, u64, vp, vp, vp, u64, vp, vp, vp,
+            u32, vp)
     if hasattr(lib, "pico_flow_group_batch_dev"):        # (an A/B build of an older round lacks it)
         sig("pico_flow_group_scratch_bytes", u64, u32, u32)
         sig("pico_flow_group_batch_dev", ctypes.c_int, vp, u64, vp, u32, vp, u32, vp, u32, u32, vp, vp, vp, vp, vp, u64, vp)

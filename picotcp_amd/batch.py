@@ -435,6 +435,53 @@ def tcp_coalesce_batch(base: torch.Tensor, seg_desc: torch.Tensor, n_seg: int, g
     return v, ol, sv
 
 
+# struct pico_csum_tcp_ack (include/pico_csum.h): the ACK batch's per-connection record
+TCP_ACK_DTYPE = np.dtype([("space", "<u4"), ("tsval", "<u4"), ("tsecr", "<u4"), ("aflags", "<u4")])
+assert TCP_ACK_DTYPE.itemsize == 16
+_ACK_OUTS = (("verdict", torch.uint8, 1, True), ("out_ack", torch.uint8, 1, True))
+
+
+def tcp_ack_batch(base: torch.Tensor, seg_desc: torch.Tensor, n_seg: int, groups: torch.Tensor, conn: torch.Tensor,
+                  out_len: torch.Tensor, seg_verdict: torch.Tensor, tmpl_base: torch.Tensor, tmpl_desc: torch.Tensor,
+                  ack: torch.Tensor, out: torch.Tensor, out_desc: torch.Tensor, flags: int = 0, stream=None,
+                  results=None):
+    """The burst's ACKs, one launch behind tcp_coalesce_batch (tcp_send_ack -> tcp_send_empty,
+    pico_tcp.c:1286-1327; tcp_sack_prepare, :1597-1657; tcp_add_options, :582-617; tcp_set_space,
+    :681-700): base / seg_desc / n_seg / groups / conn as the coalescing took them, out_len (int32[n]) and
+    seg_verdict (uint8[n_seg]) as it wrote them.  Every TCP_OLD / TCP_HELD segment's checksum is
+    verified (seg_verdict is updated in place: such a segment may become V_L4_BAD, nothing else
+    changes), and each connection with an ACCEPT, TCP_OLD or TCP_HELD segment gets one ACK frame at
+    out_desc[g].off in `out`: ack = rcv_nxt + out_len, the window from ack[g].space, the options (WS,
+    timestamps with aflags bit 0, the SACK blocks of the verified held segments with sack_ok) and both
+    checksums.  tmpl_desc[g] -> the connection's network + 20-byte TCP header template in tmpl_base;
+    ack = TCP_ACK_DTYPE records (uint8 / int32 tensor of 16 bytes a connection).  flags: reserved, 0.
+    Returns (verdict uint8[n], out_ack uint8[16 n] = the frames' descriptors, {0, 0, 0} where no ACK is
+    due); `results` may pass that pair preallocated, either of them None to skip it."""
+    dev = _on_batch_device(base, seg_desc=seg_desc, groups=groups, conn=conn, out_len=out_len, seg_verdict=seg_verdict,
+                           tmpl_base=tmpl_base, tmpl_desc=tmpl_desc, ack=ack, out=out, out_desc=out_desc)
+    _require_u8(base, "base")
+    _require_u8(tmpl_base, "tmpl_base")
+    _require_u8(out, "out")
+    n = _pairs(groups, "groups")
+    _pairs(conn, "conn", n)
+    _desc_bytes(seg_desc, n_seg, "seg_desc")
+    _desc_bytes(tmpl_desc, n, "tmpl_desc")
+    _desc_bytes(out_desc, n, "out_desc")
+    _desc_bytes(ack, n, "ack")
+    if not ack.is_contiguous():
+        raise ValueError("ack must be a contiguous tensor of 16-byte records")
+    _check_out(out_len, n, "out_len", dev, 4)
+    _check_out(seg_verdict, n_seg, "seg_verdict", dev, 1)
+    v, oa = _results(results, _ACK_OUTS, (n, 16 * n), dev)
+    lib = _lib.load()
+    _lib.check("pico_tcp_ack_batch_dev",
+               lib.pico_tcp_ack_batch_dev(_ptr(base), base.numel(), _ptr(seg_desc), n_seg, _ptr(groups), _ptr(conn), n,
+                                          _ptr(out_len), _ptr(seg_verdict), _ptr(tmpl_base), tmpl_base.numel(),
+                                          _ptr(tmpl_desc), _ptr(ack), _ptr(out), out.numel(), _ptr(out_desc), _ptr(oa),
+                                          _ptr(v), flags, _stream_handle(stream)))
+    return v, oa
+
+
 # struct pico_csum_flow_key (include/pico_csum.h): one entry of the flow grouping's connection table
 FLOW_KEY_DTYPE = np.dtype([("src", "u1", 16), ("dst", "u1", 16), ("sport", "<u2"), ("dport", "<u2"), ("family", "u1"),
                            ("reserved", "u1", 3)])

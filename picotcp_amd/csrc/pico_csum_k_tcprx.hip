@@ -3,7 +3,8 @@
 // in one pass that reads each delivered payload byte once -- and its launcher.  The inverse of the
 // send segmentation (pico_csum_k_tcpseg.hip), whose per-segment sums it keeps, and the TCP sibling
 // of the reassembly gather (pico_csum_k_frag.hip).  Helpers, the IPv4 header rules (ipv4_classify),
-// the 16-byte unit mover (unit_pair_move) and the arithmetic contract: pico_csum_dev.h.  The contract:
+// the segment parse (seg_parse, shared with pico_csum_k_tcpack.hip), the 16-byte unit mover
+// (unit_pair_move) and the arithmetic contract: pico_csum_dev.h.  The contract:
 // include/pico_csum.h, pico_tcp_coalesce_batch_dev.
 //
 // Reference: pico_transport_crc_check (stack/pico_socket.c:1916-1968), pico_tcp_input /
@@ -37,7 +38,6 @@
 namespace {
 
 constexpr uint32_t TCPRX_MAX = 512u;        // segments per connection handled on device
-constexpr uint32_t V_TCP_CTRL = 32u, V_TCP_OLD = 64u, V_TCP_HELD = 128u;   // include/pico_csum.h
 // Launch shapes, the send segmentation's two (the thresholds: SHORT_GROUPS_MIN / SHORT_SLOTS_AVG,
 // pico_csum_dev.h): four waves per connection; large batches of short groups one wave per
 // connection -- there four waves would share two to four pairs.  Measured at ONE point, 29360
@@ -71,73 +71,6 @@ struct TcpRxLds {
     uint8_t st[TCPRX_MAX];      // 0: a candidate for the chain; else the segment's verdict
     uint32_t nchain, end, anybad;
 };
-
-__device__ __forceinline__ uint32_t uni(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
-__device__ __forceinline__ uint64_t uni64(uint64_t x) { return ((uint64_t)uni((uint32_t)(x >> 32)) << 32) | uni((uint32_t)x); }
-
-// pico_seq_compare(a, b) < 0 (stack/pico_stack.c:568-591)
-__device__ __forceinline__ bool seq_before(uint32_t a, uint32_t b) {
-    return a > b ? (a - b) > 0x7FFFFFFFu : (a < b && (b - a) <= 0x7FFFFFFFu);
-}
-
-// One received frame: its verdict, 0 for a candidate of the chain (then seq, pl = payload bytes,
-// poff = the payload's offset in the frame, hsum = the pseudo header's and the TCP header's word
-// sum).  In the reference's order, no read past d.len: the network header (IPv4: ipv4_classify, the
-// fused RX batch's rules, then its header checksum, its discards and the fragment hand-off; IPv6:
-// next header 6, no extension header), the TCP header length (tcp_data_in, pico_tcp.c:1735), the
-// flags (tcp_action_by_flags) and the payload length (segment_from_frame).
-__device__ __forceinline__ uint32_t seg_parse(const TcpRxArgs& p, const pico_csum_desc_dev& d, uint32_t& seq, uint32_t& pl,
-                                              uint32_t& poff, uint32_t& hsum) {
-    seq = pl = poff = hsum = 0;
-    // (fewer than 20 bytes are MALFORMED whatever the version nibble says: the first five words are
-    // fetched together, one round trip before anything depends on them)
-    if (d.off > p.base_len || d.len > p.base_len - d.off || d.len < 20u) return V_MALFORMED;
-    const uint8_t* h = p.base + d.off;
-    uint32_t H[5];
-#pragma unroll
-    for (int m = 0; m < 5; ++m) H[m] = ld32(h + 4 * m);
-    const uint32_t ver = (H[0] & 0xFFu) >> 4;
-    uint32_t hl, tl, pseudo;
-    if (ver == 4u) {
-        const Ip4 c = ipv4_classify(H, d.len, false, false);
-        if (!c.parsed) return V_MALFORMED;
-        uint32_t acc = c.hdr20;
-        for (uint32_t k = 20u; k < c.hl; k += 4u) acc = dot2_add(ld32(h + k), acc);
-        if (finalize(acc) != 0u) return V_NET_BAD;
-        if (c.post == PV_DROP) return V_MALFORMED;
-        if (c.post == PV_FRAG) return V_FRAG;
-        if (c.proto != 6u) return V_MALFORMED;
-        hl = c.hl;
-        tl = c.tl;
-        pseudo = c.pseudo;
-    } else if (ver == 6u) {
-        if (d.len < 40u) return V_MALFORMED;
-        const uint32_t w1 = H[1];
-        if (((w1 >> 16) & 0xFFu) != 6u) return V_MALFORMED;
-        tl = bswap16(w1 & 0xFFFFu);
-        if (40u + tl > d.len) return V_MALFORMED;
-        hl = 40u;
-        // struct pico_ipv6_pseudo_hdr as LE words: the addresses, long_be(len), nxthdr 6
-        pseudo = bswap16(tl) + (6u << 8);
-#pragma unroll
-        for (uint32_t k = 8u; k < 40u; k += 4u) pseudo = dot2_add(ld32(h + k), pseudo);
-    } else {
-        return V_MALFORMED;
-    }
-    if (tl < 20u) return V_MALFORMED;
-    const uint8_t* t = h + hl;
-    const uint32_t w3 = ld32(t + 12);
-    const uint32_t thl = (w3 & 0xF0u) >> 2, flags = (w3 >> 8) & 0xFFu;
-    if (thl < 20u || thl > tl) return V_MALFORMED;
-    pl = tl - thl;
-    if (!(flags == 0x10u || flags == 0x18u) || pl == 0u) return V_TCP_CTRL;   // ACK, PSH|ACK with data: the rest is the host's
-    seq = __builtin_bswap32(ld32(t + 4));
-    uint32_t acc = pseudo;
-    for (uint32_t k = 0; k < thl; k += 4u) acc = dot2_add(ld32(t + k), acc);
-    hsum = acc;
-    poff = hl + thl;
-    return 0u;
-}
 
 // Wave 0: the chain over the candidates not struck, into L.ord / L.nchain / L.end; its members get
 // mark = round.

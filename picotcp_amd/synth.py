@@ -681,6 +681,57 @@ def tcp_rx_bursts(n_conn: int, seed: int = 83, family=4, thl=32, per=1448, max_b
     return conns, streams
 
 
+def tcp_ack_inputs(conns, seed: int = 89, space=16384, ts_ok=None, region: int = 100, out_off: int = 0, align=0):
+    """What pico_tcp_ack_batch_dev takes beside the coalescing's arrays, for `conns` (tcp_rx_bursts' /
+    tcp_rx_pack's list): per connection a header template answering its first frame -- the network
+    header with the addresses swapped (IPv4: IHL 5, its own id, ttl 64; IPv6: no extension header) and
+    a 20-byte TCP header with the ports swapped, a random seq (snd_nxt) and random bytes in the fields
+    the batch does not read -- at `align` mod 16 (one value or one per connection), and a
+    pico_csum_tcp_ack record (space: one value or one per connection; ts_ok: likewise, None = seeded).
+    Output regions of `region` bytes back to back, each at out_off mod 16.  Returns (template buffer,
+    template offsets uint64, template bytes uint32, ack records as a structured array (space, tsval,
+    tsecr, aflags), out offsets uint64, out capacities uint32, out_len)."""
+    rng = np.random.default_rng(seed)
+    n = len(conns)
+    aligns = np.broadcast_to(np.asarray(align, dtype=np.int64), (n,))
+    spaces = np.broadcast_to(np.asarray(space, dtype=np.uint32), (n,))
+    tss = rng.integers(0, 2, n) if ts_ok is None else np.broadcast_to(np.asarray(ts_ok, dtype=np.int64), (n,))
+    ack = np.zeros(n, np.dtype([("space", "<u4"), ("tsval", "<u4"), ("tsecr", "<u4"), ("aflags", "<u4")]))
+    ack["space"], ack["aflags"] = spaces, tss
+    ack["tsval"] = rng.integers(0, 1 << 32, n, dtype=np.uint64)
+    ack["tsecr"] = rng.integers(0, 1 << 32, n, dtype=np.uint64)
+    pieces, off, ln = [], np.zeros(n, np.uint64), np.zeros(n, np.uint32)
+    pos = 0
+    for g, c in enumerate(conns):
+        f = np.asarray(c[0][0], dtype=np.uint8)
+        if int(f[0]) >> 4 == 6:
+            h = f[:40].copy()
+            h[8:24], h[24:40] = f[24:40], f[8:24]
+            h[4:6] = rng.integers(0, 256, 2, dtype=np.uint8)          # (payload length: not read)
+            t0 = 40
+        else:
+            h = rng.integers(0, 256, 20, dtype=np.uint8)              # (len, frag, crc: not read)
+            h[0], h[1], h[8], h[9] = 0x45, f[1], 64, 6
+            h[12:16], h[16:20] = f[16:20], f[12:16]
+            t0 = 4 * (int(f[0]) & 15)
+        t = rng.integers(0, 256, 20, dtype=np.uint8)                  # (ack, thl, flags, rwnd, crc: not read)
+        t[0:2], t[2:4] = f[t0 + 2:t0 + 4], f[t0:t0 + 2]
+        pos += (int(aligns[g]) - pos) % 16
+        off[g], ln[g] = pos, h.size + 20
+        pieces.append(np.concatenate([h, t]))
+        pos += pieces[-1].size
+    buf = random_bytes(seed ^ 0x51C3, pos + 16)
+    for g in range(n):
+        buf[int(off[g]):int(off[g]) + pieces[g].size] = pieces[g]
+    ooff = np.zeros(n, np.uint64)
+    pos = 0
+    for g in range(n):
+        pos += (out_off - pos) % 16
+        ooff[g] = pos
+        pos += region
+    return buf, off, ln, ack, ooff, np.full(n, region, np.uint32), pos + 16
+
+
 def interleave_groups(desc, groups, seed: int = 91):
     """A seeded merge of group-contiguous frames into one arrival order that keeps each group's own order
     (what a link delivers when several flows send at once): desc = the frames' descriptors (any array
