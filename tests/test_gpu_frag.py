@@ -3,7 +3,14 @@ pico_ipv6_reassemble_batch_dev) against the oracle on seeded fragment sets -- ou
 arrival, repeated offsets, holes, overlaps, fragments behind the completing one, odd tails, UDP
 crc 0, TCP / UDP / ICMP / other protocols, hop-by-hop headers before the fragment header, both
 IPv6 dispatches, 64512-byte datagrams -- and against the reference-pinned fixture
-(tests/golden/ref_reasm_cases.npz) -- bit-exact on the outputs and on every reassembled byte."""
+(tests/golden/ref_reasm_cases.npz) -- bit-exact on the outputs and on every reassembled byte.
+
+What is compared (check, _check_flat, test_reference_fixture): the verdicts, lengths and checksums;
+each reassembled datagram's header + len bytes; and the WHOLE output buffer, pre-filled with the
+canary 0xA5 on both sides, at every byte the contract specifies -- all but unspecified_mask
+(tests/frag_regions.py): a not-reassembled datagram's region and a reassembled one's capacity past
+its end.  So every test that goes through them, tests/test_gpu_frag_fuzz.py included, also asserts
+"no byte outside the region is written".  Tight regions: tests/test_gpu_frag_regions.py."""
 from __future__ import annotations
 
 import numpy as np
@@ -13,6 +20,7 @@ import torch
 from oracle import oracle as O
 from picotcp_amd import batch, synth
 from tests import golden_data as G
+from tests.frag_regions import CANARY, same_outside, unspecified_mask
 from tests.test_frag_oracle import MF, frame, run
 from tests.gpu_util import pairs_dev, to_dev
 
@@ -30,7 +38,7 @@ def reasm_path(request):
 
 
 def gpu_reassemble(buf, d, grp, od, out_size, v6=False, nx=False):
-    out = torch.zeros(out_size, dtype=torch.uint8, device="cuda:0")
+    out = torch.full((out_size,), CANARY, dtype=torch.uint8, device="cuda:0")
     args = (buf if isinstance(buf, torch.Tensor) else to_dev(buf), to_dev(d.view(np.uint8)), d.size,
             pairs_dev(grp), out, to_dev(od.view(np.uint8)))
     if v6:
@@ -44,7 +52,7 @@ def gpu_reassemble(buf, d, grp, od, out_size, v6=False, nx=False):
 def check(buf, d, grp, od, out_size, v6=False, nx=False, far=None):
     """Oracle on (buf, d) against the GPU on the same -- or on far = (device buffer, descriptors):
     the same fragments laid out elsewhere."""
-    out_o = np.zeros(out_size, np.uint8)
+    out_o = np.full(out_size, CANARY, np.uint8)
     if v6:
         wl, w4, wv = O.ipv6_reassemble(buf, d, grp, out_o, od, nxthdr_dispatch=nx)
     else:
@@ -57,6 +65,7 @@ def check(buf, d, grp, od, out_size, v6=False, nx=False, far=None):
     for g in np.flatnonzero(wv != 8):                   # every reassembled byte
         o, n = int(od["off"][g]), H + int(wl[g])
         np.testing.assert_array_equal(out_g[o:o + n], out_o[o:o + n], err_msg=f"datagram {g}")
+    same_outside(out_g, out_o, unspecified_mask(out_size, od, wv, wl, H))   # and nothing outside a region
     return wl, wv
 
 
@@ -157,9 +166,12 @@ def test_reference_fixture(fam, nx):
     np.testing.assert_array_equal(gl, c[p + "len"])
     np.testing.assert_array_equal(g4, c[p + ("l4_nx" if nx else "l4")])
     H = 40 if fam == "v6" else 20
+    want = np.full(out_g.size, CANARY, np.uint8)         # the fixture's bytes where a datagram is, else the canary
     for g in np.flatnonzero(gv != 8):
         o, n = int(c[p + "out_off"][g]), H + int(gl[g])
         np.testing.assert_array_equal(out_g[o:o + n], c[p + "exp_out"][o:o + n], err_msg=f"datagram {g}")
+        want[o:o + n] = c[p + "exp_out"][o:o + n]
+    same_outside(out_g, want, unspecified_mask(out_g.size, od, gv, gl, H))
 
 
 def test_ipv6_reassembly_limits():
@@ -228,7 +240,7 @@ def _flat_case(n, seed):
     buf, off, flen, grp = synth.ipv4_fragments(lens, seed=seed, proto=6, frag_payload=552)
     d = G.ipv4_desc(off, flen)
     od, size = layout(lens, shift=4)
-    out_o = np.zeros(size, np.uint8)
+    out_o = np.full(size, CANARY, np.uint8)
     want = O.ipv4_reassemble(buf, d, grp, out_o, od)
     dev = (to_dev(buf), to_dev(d.view(np.uint8)), d.size, pairs_dev(grp), to_dev(od.view(np.uint8)))
     return dev, od, size, want, out_o
@@ -243,13 +255,18 @@ def _check_flat(res, out, od, want, out_o):
     for g in np.flatnonzero(want[2] != 8):
         o, n = int(od["off"][g]), 20 + int(want[0][g])
         np.testing.assert_array_equal(o_g[o:o + n], out_o[o:o + n], err_msg=f"datagram {g}")
+    same_outside(o_g, out_o, unspecified_mask(o_g.size, od, want[2], want[0], 20))
+
+
+def _canary_out(size):
+    return torch.full((size,), CANARY, dtype=torch.uint8, device="cuda:0")
 
 
 def test_flat_grid_graph_capture():
     """The flat grid captured into a graph (its scratch then owned by the graph): replays match the
     oracle, and eager calls afterwards too (after the graph is destroyed as well)."""
     (b, d, nf, grp, od_d), od, size, want, out_o = _flat_case(1500, 71)
-    outs = [torch.zeros(size, dtype=torch.uint8, device="cuda:0") for _ in range(2)]
+    outs = [_canary_out(size) for _ in range(2)]
     res = [batch.ipv4_reassemble_batch(b, d, nf, grp, o, od_d) for o in outs]   # warm (eager)
     torch.cuda.synchronize()
     g = torch.cuda.CUDAGraph()
@@ -262,20 +279,21 @@ def test_flat_grid_graph_capture():
     torch.cuda.current_stream().wait_stream(s)
     for _ in range(3):
         for o, r in zip(outs, res):
-            o.zero_()
+            o.fill_(CANARY)
             for x in r:
                 x.zero_()
         g.replay()
         torch.cuda.synchronize()
         for o, r in zip(outs, res):
             _check_flat(r, o, od, want, out_o)
-    o = torch.zeros(size, dtype=torch.uint8, device="cuda:0")
+    o = _canary_out(size)
+    s.wait_stream(torch.cuda.current_stream())           # the fill before the gather
     r = batch.ipv4_reassemble_batch(b, d, nf, grp, o, od_d, stream=s)
     torch.cuda.synchronize()
     _check_flat(r, o, od, want, out_o)
     del g                                                # the graph's scratch freed by the next call
     torch.cuda.synchronize()
-    o.zero_()
+    o.fill_(CANARY)
     r = batch.ipv4_reassemble_batch(b, d, nf, grp, o, od_d)
     torch.cuda.synchronize()
     _check_flat(r, o, od, want, out_o)
@@ -290,7 +308,7 @@ def test_flat_grid_streams_and_sizes():
     runs = []
     for case, st in ((small, s1), (small, s2), (large, s1), (large, s2), (small, s1)):
         (b, d, nf, grp, od_d), od, size, want, out_o = case
-        o = torch.zeros(size, dtype=torch.uint8, device="cuda:0")
+        o = _canary_out(size)
         st.wait_stream(torch.cuda.current_stream())
         r = batch.ipv4_reassemble_batch(b, d, nf, grp, o, od_d, stream=st)
         runs.append((r, o, case))

@@ -9,7 +9,8 @@ flipped, a truncated descriptor -- arrival order shuffled.  600-1000 datagrams a
 over 512 fragments a datagram), under every setting of pico_csum_set_reasm_flat: the launcher's
 choice, the flat grid forced (planners with one or two fragments a lane, gather waves, the finish
 and its workgroup path for SLOW plans) and one workgroup per datagram.  Every verdict, length,
-checksum and reassembled byte is compared."""
+checksum and reassembled byte is compared, and (check of tests/test_gpu_frag.py) every byte of the
+canary-filled output buffer that the contract specifies: nothing is written outside a region."""
 from __future__ import annotations
 
 import numpy as np
