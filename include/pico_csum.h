@@ -59,7 +59,9 @@ extern "C" {
  *      returns -- likewise;
  *   4 (added, no bump): pico_flow_group_batch_dev, pico_flow_group_scratch_bytes, struct pico_csum_flow_key
  *      and the PICO_CSUM_FLOW_* modes -- likewise;
- *   4 (added, no bump): pico_tcp_ack_batch_dev and struct pico_csum_tcp_ack -- likewise. */
+ *   4 (added, no bump): pico_tcp_ack_batch_dev and struct pico_csum_tcp_ack -- likewise;
+ *   4 (added, no bump): pico_icmp4_reply_batch_dev, struct pico_csum_icmp4_req and struct
+ *      pico_csum_icmp4_state -- likewise. */
 #define PICO_CSUM_ABI_VERSION 4
 
 /* picoTCP pico_err values used here (include/pico_protocol.h:27,31,38 + ENODEV) */
@@ -652,6 +654,84 @@ int pico_tcp_ack_batch_dev(const void *d_base, uint64_t base_len, const struct p
                            const struct pico_csum_desc *d_tmpl, const struct pico_csum_tcp_ack *d_ack, void *d_out,
                            uint64_t out_len, const struct pico_csum_desc *d_out_desc, struct pico_csum_desc *d_out_ack,
                            uint8_t *d_verdict, uint32_t flags, void *stream);
+
+/* A burst's ICMPv4 answers: the echo replies and the notices (destination unreachable, time exceeded,
+ * parameter problem) that the verdicts of the RX, forwarding and reassembly batches call for, each built
+ * on the device as a finished IPv4 datagram in its own output region.  The batch form of
+ * pico_icmp4_process_in (modules/pico_icmp4.c:47-85) with pico_icmp4_checksum (:30-41), pico_ipv4_rebound
+ * and pico_ipv4_frame_push (modules/pico_ipv4.c:1512-1533, :1039-1079), and of pico_icmp4_notify
+ * (modules/pico_icmp4.c:106-141; its callers: stack/pico_stack.c:82-183, pico_ipv4.c:1553, :1595-1597).  An
+ * echo reply is a copy and a sum of up to 64 KiB: one pass reads each transport byte once, where the
+ * reference rewrites the frame, sums the whole transport again and pushes it.  The host chooses which
+ * datagram gets which record, looks up the route (src), keeps the id counter, limits the rate and keeps
+ * ping_recv_reply.
+ *   d_desc[i]  the datagram that is answered: desc.off -> its IPv4 header, desc.len = bytes available from
+ *              there (nothing past it or past base_len contributes; reads follow the whole-16-byte-block
+ *              rule above); desc.seed is not read.
+ *   d_req[i]   struct pico_csum_icmp4_req, host-filled: src = the answer's source (the address of the link
+ *              the route to the asker uses, :1055, as stored in a frame), id = the IPv4 id (host order,
+ *              :1041), type 0 = answer as pico_icmp4_process_in does, type 3 / 11 / 12 with any code =
+ *              the notice to send.
+ *   d_out_desc[i]  the answer's region in d_out (off any alignment, len = capacity).
+ *   d_out_ans[i]   {the answer's offset in d_out, its length, 0} -- with d_out, the input of the TX path,
+ *              of pico_ipv4_checksum_batch_dev or of pico_ipv4_fragment_batch_dev as it is -- or {0, 0, 0}.
+ * Echo (type 0).  A record is an echo request when it parses -- version 4, IHL >= 5, proto 1, IHL 4 + 8 <=
+ * len field <= desc.len -- and its ICMP type is 8 (:55).  One that parses with another ICMP type is
+ * V_UNTOUCHED (the NAT batch's bit) and nothing is written: echo replies, unreachables and the rest stay
+ * the host's (ping_recv_reply :77, pico_ipv4_unreachable :74).
+ *   duplicates (:61-69)  an echo request whose (id, seq) equals that of the nearest earlier echo request of
+ *              the batch -- answered or not: a dropped duplicate leaves the statics equal -- or, when there
+ *              is none, of the carried state with seen != 0, is V_DUPLICATE and nothing is written.  The
+ *              compare ignores the source address, as the reference's does.  After the batch d_state holds
+ *              the last echo request's pair, as stored in its frame, and seen = 1 (firstpkt, last_id,
+ *              last_seq); a batch without an echo request leaves it as it was.  d_state NULL: nothing is
+ *              carried in and nothing is kept.  A MALFORMED record takes no part.
+ *   the answer  20 + T bytes, T = len field - IHL 4: the header 45, tos 0, len, req.id, the request's frag
+ *              field as it lies (f->frag = short_be(hdr->frag), pico_ipv4.c:402, comes back through
+ *              :1072-1075), ttl 64, proto 1, pico_ipv4_checksum (:1079), src = req.src, dst = the request's
+ *              source (:1527); then the request's T transport bytes with type 0 (:56) and crc =
+ *              pico_icmp4_checksum over the bytes AS COPIED -- never derived from the request's crc: the
+ *              reference does not verify an echo request's checksum and answers a corrupted one with a
+ *              valid reply.  Bytes behind the datagram (padding, a trailer) are not copied.  tos 0 / ttl
+ *              64 are what send_tos / send_ttl of a received frame give (:1050-1057), as the captured
+ *              replies show (tests/golden/ref_icmp4_cases.npz).
+ * Notices (type 3, 11, 12; any code): pico_icmp4_notify literally.  q = min(len field, 28) bytes are quoted
+ * from the IPv4 header on WHATEVER the IHL (:118-126, :137: with options the quote holds option bytes where
+ * the transport's first 8 would be -- kept), as they lie (behind the forwarding batch: with the decremented
+ * ttl).  The answer is 20 + 8 + q bytes: the header as above with frag 0 (the answer frame's own f->frag),
+ * then type, code, crc, 00 00, 05 dc (ipm_void, ipm_nmtu = 1500 on every notice, :133-134), the quote; dst =
+ * the datagram's source (:139).  Nothing but the len field is parsed.
+ *   d_verdict[i]  ACCEPT = the answer is written and d_out_ans[i] set; V_UNTOUCHED, V_DUPLICATE (the
+ *              forwarding batch's bit) as above; MALFORMED = nothing of the region is written: a descriptor
+ *              past base_len or of fewer than 20 bytes, a req.type outside {0, 3, 11, 12}, an echo record
+ *              that fails the parse, a notice with len field < 20 or q > desc.len, and -- for a record that
+ *              would be answered -- a region past out_len or smaller than the answer.  For all three
+ *              d_out_ans[i] = {0, 0, 0}.
+ * No byte outside a region is written, and inside it only the answer's own bytes.  Regions must not
+ * overlap.  Ids of unanswered records are simply not used (the reference's single counter would not skip
+ * them; the peer cannot tell).  Documented differences from the reference: (1) a request with IPv4 options
+ * is answered with a 20-byte header followed by its transport -- the reference pushes vhl = 45 (:1039) over
+ * a header that still holds the options, which no receiver reads as a reply; the evident intent is restated,
+ * as the fragmentation batch does for frag; (2) an answer longer than the MTU is written whole (len up to
+ * 65535) where the reference splits it (pico_ipv4_rebound_large, :1464-1510): it goes through
+ * pico_ipv4_fragment_batch_dev unchanged, which states the same split.
+ * Host checks, -EINVAL before any launch: a NULL required pointer (all but d_state and d_out_ans); d_desc,
+ * d_out_desc or d_out_ans not 16-byte aligned; d_req or d_state not 4-byte aligned; flags != 0 (reserved).
+ * n == 0 is a no-op; without a device -ENODEV.  Four launches on one stream (verdicts; the duplicates'
+ * backward scan; one wave per two records for the answers, per record when base_len >= 1024 n; one
+ * workgroup for the state -- three without d_state), no allocation, no library scratch, no spin-wait, no
+ * host synchronisation: capturable behind the batch whose verdicts chose the records.  Results never depend
+ * on the launch shape. */
+struct pico_csum_icmp4_req {   /* 8 bytes, per record, host-filled */
+    uint32_t src;              /* the answer's source: the link address the route to the asker uses, as stored in a frame */
+    uint16_t id;               /* the IPv4 id to use, host order */
+    uint8_t  type, code;       /* type 0: answer as pico_icmp4_process_in does (echo); 3 / 11 / 12: the notice to send */
+};
+struct pico_csum_icmp4_state { uint32_t seen; uint16_t id, seq; };   /* process_in's statics: firstpkt, last_id, last_seq */
+int pico_icmp4_reply_batch_dev(const void *d_base, uint64_t base_len, const struct pico_csum_desc *d_desc, uint32_t n,
+                               const struct pico_csum_icmp4_req *d_req, struct pico_csum_icmp4_state *d_state,
+                               void *d_out, uint64_t out_len, const struct pico_csum_desc *d_out_desc,
+                               struct pico_csum_desc *d_out_ans, uint8_t *d_verdict, uint32_t flags, void *stream);
 
 /* Flow grouping: a verified burst, in arrival order, becomes the inputs of the three gather batches above
  * -- each flow's frames contiguous, in arrival order, and the groups[] over them -- on the device, with no

@@ -482,6 +482,57 @@ def tcp_ack_batch(base: torch.Tensor, seg_desc: torch.Tensor, n_seg: int, groups
     return v, oa
 
 
+# struct pico_csum_icmp4_req / pico_csum_icmp4_state (include/pico_csum.h): the ICMPv4 answers' per-record
+# request and the carried duplicate state
+ICMP4_REQ_DTYPE = np.dtype([("src", "<u4"), ("id", "<u2"), ("type", "u1"), ("code", "u1")])
+ICMP4_STATE_DTYPE = np.dtype([("seen", "<u4"), ("id", "<u2"), ("seq", "<u2")])
+assert ICMP4_REQ_DTYPE.itemsize == 8 and ICMP4_STATE_DTYPE.itemsize == 8
+_ICMP4_OUTS = (("verdict", torch.uint8, 1, False), ("out_ans", torch.uint8, 1, True))
+
+
+def icmp4_state(device) -> torch.Tensor:
+    """An echo duplicate state (struct pico_csum_icmp4_state) at the reference's initial value (firstpkt:
+    seen = 0)."""
+    return torch.zeros(ICMP4_STATE_DTYPE.itemsize, dtype=torch.uint8, device=device)
+
+
+def icmp4_reply_batch(base: torch.Tensor, desc: torch.Tensor, n: int, req: torch.Tensor, out: torch.Tensor,
+                      out_desc: torch.Tensor, *, state: torch.Tensor | None, flags: int = 0, stream=None, results=None):
+    """A burst's ICMPv4 answers (pico_icmp4_process_in, pico_icmp4.c:47-85, with pico_icmp4_checksum :30-41
+    and pico_ipv4_rebound / pico_ipv4_frame_push, pico_ipv4.c:1512-1533, :1039-1079; pico_icmp4_notify,
+    pico_icmp4.c:106-141): desc = one answered datagram per descriptor (off -> its IPv4 header, len = bytes
+    available), req = ICMP4_REQ_DTYPE records (uint8 / int32 tensor of 8 bytes a record: the answer's source
+    as stored, its IPv4 id, type 0 = echo reply to an echo request, 3 / 11 / 12 + code = that notice), out =
+    uint8 device buffer, out_desc[i] = the answer's region (off, capacity).  `state` (icmp4_state()) carries
+    the last echo request's (id, seq) from one call to the next, as the reference's statics do; state=None
+    is the explicit one-shot mode (nothing carried, nothing kept).  flags: reserved, 0.  Returns (verdict
+    uint8[n]: V_ACCEPT, V_UNTOUCHED, V_DUPLICATE or V_MALFORMED; out_ans uint8[16 n] = the answers'
+    descriptors, {0, 0, 0} where none was written); `results` may pass that pair preallocated, out_ans None
+    to skip it."""
+    tensors = dict(desc=desc, req=req, out=out, out_desc=out_desc)
+    if state is not None:
+        tensors["state"] = state
+    dev = _on_batch_device(base, **tensors)
+    _require_u8(base, "base")
+    _require_u8(out, "out")
+    if n < 0:
+        raise ValueError(f"n = {n}")
+    _desc_bytes(desc, n, "desc")
+    _desc_bytes(out_desc, n, "out_desc")
+    if not req.is_contiguous() or req.numel() * req.element_size() < 8 * n:
+        raise ValueError(f"req must be a contiguous tensor of {n} 8-byte records")
+    if state is not None and (not state.is_contiguous() or state.numel() * state.element_size() < 8):
+        raise ValueError("state must be a contiguous 8-byte tensor (icmp4_state())")
+    if results is not None and results[0] is None:
+        raise ValueError("verdict is required: the launches hand their work on through it")
+    v, oa = _results(results, _ICMP4_OUTS, (n, 16 * n), dev)
+    lib = _lib.load()
+    _lib.check("pico_icmp4_reply_batch_dev",
+               lib.pico_icmp4_reply_batch_dev(_ptr(base), base.numel(), _ptr(desc), n, _ptr(req), _ptr(state), _ptr(out),
+                                              out.numel(), _ptr(out_desc), _ptr(oa), _ptr(v), flags, _stream_handle(stream)))
+    return v, oa
+
+
 # struct pico_csum_flow_key (include/pico_csum.h): one entry of the flow grouping's connection table
 FLOW_KEY_DTYPE = np.dtype([("src", "u1", 16), ("dst", "u1", 16), ("sport", "<u2"), ("dport", "<u2"), ("family", "u1"),
                            ("reserved", "u1", 3)])

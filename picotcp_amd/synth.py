@@ -732,6 +732,83 @@ def tcp_ack_inputs(conns, seed: int = 89, space=16384, ts_ok=None, region: int =
     return buf, off, ln, ack, ooff, np.full(n, region, np.uint32), pos + 16
 
 
+def icmp4_echo_request(rng, T: int, ident: int = 0, seq: int = 0, ihl: int = 5, frag: int = 0x4000, src=None, dst=None,
+                       icmp_type: int = 8, bad_crc: bool = False) -> np.ndarray:
+    """One IPv4 datagram with an ICMP message of T >= 8 transport bytes (type 8: an echo request) behind
+    4 * ihl header bytes (options: random bytes), both checksums valid unless bad_crc flips a bit of the
+    ICMP one."""
+    hl = 4 * ihl
+    f = np.zeros(hl + T, np.uint8)
+    f[0], f[1], f[8], f[9] = 0x40 | ihl, int(rng.integers(256)), int(rng.integers(1, 256)), 1
+    f[2], f[3] = (hl + T) >> 8, (hl + T) & 0xFF
+    f[4:6] = rng.integers(0, 256, 2, dtype=np.uint8)
+    f[6], f[7] = frag >> 8, frag & 0xFF
+    f[12:16] = rng.integers(1, 224, 4, dtype=np.uint8) if src is None else np.frombuffer(bytes(src), np.uint8)
+    f[16:20] = rng.integers(1, 224, 4, dtype=np.uint8) if dst is None else np.frombuffer(bytes(dst), np.uint8)
+    f[20:hl] = rng.integers(0, 256, hl - 20, dtype=np.uint8)
+    c = _csum16(f[:hl])
+    f[10], f[11] = c >> 8, c & 0xFF
+    t = f[hl:]
+    t[8:] = rng.integers(0, 256, T - 8, dtype=np.uint8)
+    t[0], t[1] = icmp_type, 0
+    t[4], t[5], t[6], t[7] = ident >> 8, ident & 0xFF, seq >> 8, seq & 0xFF
+    c = _csum16(t)
+    t[2], t[3] = c >> 8, c & 0xFF
+    if bad_crc:
+        t[3] ^= 0x10
+    return f
+
+
+def _csum16(b: np.ndarray) -> int:
+    """The Internet checksum of b as the big-endian field value (numpy; the builders' own, not the oracle's)."""
+    a = np.asarray(b, dtype=np.uint8)
+    if a.size & 1:
+        a = np.concatenate([a, np.zeros(1, np.uint8)])
+    s = int((a[0::2].astype(np.uint64) << 8).sum() + a[1::2].astype(np.uint64).sum())
+    while s >> 16:
+        s = (s & 0xFFFF) + (s >> 16)
+    return ~s & 0xFFFF
+
+
+def icmp4_burst(dgrams, types, codes=0, seed: int = 97, align=0, slack=0, out_off=0, region=None, local=(10, 0, 0, 1)):
+    """The inputs of pico_icmp4_reply_batch_dev for the datagrams `dgrams` (uint8 arrays, the IPv4 header
+    first): record i answers datagram i with types[i] (0: echo; 3 / 11 / 12: that notice, codes[i]).  The
+    datagrams lie in one buffer at `align` mod 16 each with `slack` readable bytes behind (desc.len =
+    bytes + slack; a negative slack cuts the descriptor short), the answers' regions back to back at
+    `out_off` mod 16 each, `region` bytes or -- None -- exactly the answer's size (tight).  align, slack,
+    out_off, codes: one value or one per record.  Returns (buffer, offsets uint64, lengths uint32, req
+    records (src, id, type, code), out offsets uint64, out capacities uint32, out_len = 16 bytes past the last region)."""
+    n = len(dgrams)
+    rng = np.random.default_rng(seed)
+    bc = lambda x: np.broadcast_to(np.asarray(x, dtype=np.int64), (n,))
+    aligns, slacks, ooffs, cds, tps = bc(align), bc(slack), bc(out_off), bc(codes), bc(types)
+    off, ln = np.zeros(n, np.uint64), np.zeros(n, np.uint32)
+    pos = 0
+    for i, f in enumerate(dgrams):
+        pos += (int(aligns[i]) - pos) % 16
+        off[i], ln[i] = pos, len(f) + int(slacks[i])
+        pos += len(f) + max(int(slacks[i]), 0)
+    buf = random_bytes(seed ^ 0x1C3F, pos)
+    for i, f in enumerate(dgrams):
+        buf[int(off[i]):int(off[i]) + len(f)] = f
+    req = np.zeros(n, np.dtype([("src", "<u4"), ("id", "<u2"), ("type", "u1"), ("code", "u1")]))
+    req["src"] = int.from_bytes(bytes(local), "little")
+    req["id"] = (int(rng.integers(0, 1 << 16)) + np.arange(n)) & 0xFFFF
+    req["type"], req["code"] = tps, cds
+    cap = np.zeros(n, np.uint32)
+    for i, f in enumerate(dgrams):
+        tot = (int(f[2]) << 8 | int(f[3])) if len(f) >= 4 else 0
+        need = 20 + max(tot - 4 * (int(f[0]) & 15), 0) if tps[i] == 0 else 28 + min(tot, 28)
+        cap[i] = need if region is None else region
+    ooff = np.zeros(n, np.uint64)
+    pos = 0
+    for i in range(n):
+        pos += (int(ooffs[i]) - pos) % 16
+        ooff[i] = pos
+        pos += int(cap[i])
+    return buf, off, ln, req, ooff, cap, pos + 16
+
+
 def interleave_groups(desc, groups, seed: int = 91):
     """A seeded merge of group-contiguous frames into one arrival order that keeps each group's own order
     (what a link delivers when several flows send at once): desc = the frames' descriptors (any array
