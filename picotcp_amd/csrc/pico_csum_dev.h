@@ -1,12 +1,15 @@
 // pico_csum_dev.h -- device helpers shared by the gfx950 kernel TUs of libpicocsum
 // (pico_csum_k_raw.hip, pico_csum_k_sorted.hip, pico_csum_k_frag.hip, pico_csum_k_fragtx.hip,
-// pico_csum_k_tcpseg.hip, pico_csum_k_tcprx.hip, pico_csum_k_tcpack.hip, pico_csum_k_icmp.hip).
+// pico_csum_k_tcpseg.hip, pico_csum_k_tcprx.hip, pico_csum_k_tcpack.hip, pico_csum_k_icmp.hip,
+// pico_csum_k_flow.hip).
 // Header-only, internal; everything lives in an anonymous namespace (one copy per TU).
 // In order: the checksum arithmetic and the lane-group sums (every TU); windowed buffer loads
 // (_k_raw, _k_sorted, _k_frag); the IPv4 header rules (_k_sorted, _k_tcprx); the IPv6 extension-header
-// walk (_k_sorted, _k_frag); the 16-byte unit mover, the output-slot rules and the launch-shape
-// thresholds of the scatter / gather batches (_k_fragtx, _k_tcpseg, _k_tcprx; the mover: _k_icmp too); the
-// dispatch shapes.
+// walk (_k_sorted, _k_frag, _k_flow); the 16-byte unit mover and the output-slot rules of the scatter /
+// gather batches (_k_fragtx, _k_tcpseg, _k_tcprx; the mover: _k_icmp too); the frames written by the
+// device: the descriptor-inside-buffer rule (_k_frag and every batch of K8-K10, K12, K13), the header
+// word's halves and store (_k_tcpseg, _k_tcpack, _k_icmp); the received TCP segment's parse (_k_tcprx, _k_tcpack); the launch-shape thresholds
+// and their decision (_k_fragtx, _k_tcpseg, _k_tcprx, _k_tcpack); the dispatch shapes.
 //
 // The kernels of picoTCP's Internet checksum.
 //
@@ -664,6 +667,32 @@ __device__ __forceinline__ void write_slots(pico_csum_desc_dev* slot, uint32_t r
     }
 }
 
+// ---------------------------------------------------------------- frames written by the device (K9, K12, K13)
+//
+// What pico_csum_k_tcpseg.hip, pico_csum_k_tcpack.hip and pico_csum_k_icmp.hip share: a lane per 32-bit
+// header word, its halves summed and the word stored.  The TCP/IP template's check and word sums stay in
+// _k_tcpseg and _k_tcpack, each its own: a shared check cost both kernels 4-6 % where the per-group work
+// dominates (profiles/header_words/ab_variants.txt).
+
+// Descriptor d does NOT lie inside a buffer of L bytes: THE rule for every descriptor a batch takes --
+// input, template, output region -- in seg_parse, _k_frag, _k_fragtx, _k_tcpseg, _k_tcprx, _k_tcpack and
+// _k_icmp; a new batch uses it too.  Only _k_flow spells it out (net_region): with the helper its device
+// code differed from the tuned text; _k_raw and _k_sorted test loose (off, len) pairs, not descriptors.
+__device__ __forceinline__ bool span_out(const pico_csum_desc_dev& d, uint64_t L) { return d.off > L || d.len > L - d.off; }
+
+// The 16-bit halves of header word w that enter a sum (_k_tcpseg, _k_tcpack, _k_icmp).
+__device__ __forceinline__ uint32_t halves(uint32_t w, bool lo = true, bool hi = true) {
+    return (lo ? w & 0xFFFFu : 0u) + (hi ? w >> 16 : 0u);
+}
+
+// The low nb bytes of header word v at t (_k_tcpseg, _k_tcpack; _k_icmp, whose quote may end inside a
+// word): one 32-bit store for a whole word at a 4-byte aligned address, byte stores otherwise.  Not
+// store_le: its 16-bit stores at even addresses are the sorted kernel's.
+__device__ __forceinline__ void store_word(uint8_t* t, uint32_t v, uint32_t nb = 4u) {
+    if (nb == 4u && (reinterpret_cast<uint64_t>(t) & 3u) == 0u) *reinterpret_cast<uint32_t*>(t) = v;
+    else for (uint32_t k = 0; k < nb; ++k) t[k] = (uint8_t)(v >> (8u * k));
+}
+
 // ---------------------------------------------------------------- received TCP segments (K10, K12)
 //
 // What pico_csum_k_tcprx.hip and pico_csum_k_tcpack.hip share: the coalescing batch's verdict values, the
@@ -690,7 +719,7 @@ __device__ __forceinline__ uint32_t seg_parse(const Args& p, const pico_csum_des
     seq = pl = poff = hsum = 0;
     // (fewer than 20 bytes are MALFORMED whatever the version nibble says: the first five words are
     // fetched together, one round trip before anything depends on them)
-    if (d.off > p.base_len || d.len > p.base_len - d.off || d.len < 20u) return V_MALFORMED;
+    if (span_out(d, p.base_len) || d.len < 20u) return V_MALFORMED;
     const uint8_t* h = p.base + d.off;
     uint32_t H[5];
 #pragma unroll
@@ -745,6 +774,11 @@ __device__ __forceinline__ uint32_t seg_parse(const Args& p, const pico_csum_des
 // its two shapes at ONE point, 29360 groups of 7 members (profiles/tcpseg/ab_shapes.txt,
 // profiles/tcprx/ab_shapes.txt), and measured neither threshold.
 constexpr uint32_t SHORT_GROUPS_MIN = 3072u, SHORT_SLOTS_AVG = 16u;
+
+// The launchers' decision (_k_fragtx, _k_tcpseg, _k_tcprx, _k_tcpack): one wave per group.
+inline bool short_groups(uint32_t n_groups, uint32_t n_members) {
+    return n_groups >= SHORT_GROUPS_MIN && (uint64_t)n_members <= (uint64_t)SHORT_SLOTS_AVG * n_groups;
+}
 
 struct FlatArgs {
     uint8_t* base;

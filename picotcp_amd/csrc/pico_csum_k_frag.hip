@@ -247,7 +247,7 @@ template <bool V6>
 __device__ __forceinline__ bool frag_parse(const FragArgs& p, const pico_csum_desc_dev& d, bool pre, uint4 v0, uint4 v40,
                                            uint32_t& key, uint32_t& tl, uint32_t& hl, uint32_t& pr) {
     key = tl = hl = pr = 0;
-    if (d.len < (V6 ? 40u : 20u) || d.off > p.base_len || d.len > p.base_len - d.off) return false;
+    if (d.len < (V6 ? 40u : 20u) || span_out(d, p.base_len)) return false;
     const uint8_t* h = p.base + d.off;
     const FragFields f = pre ? fields_regs<V6>(v0, v40) : fields_bytes<V6>(h, d.len);
     return frag_rules<V6>(f, h, d.len, key, tl, hl, pr);
@@ -296,7 +296,7 @@ __device__ __forceinline__ Group group_of(const FragArgs& p, uint32_t g) {
     G.cnt = p.grp[2 * g + 1];
     G.od = p.odesc[g];
     G.bad0 = G.cnt == 0 || G.cnt > FRAG_MAX || G.first > p.n_frag || G.cnt > p.n_frag - G.first || (G.od.off & 3u) != 0 ||
-             G.od.off > p.out_len || G.od.len > p.out_len - G.od.off || G.od.len < HDR;
+             span_out(G.od, p.out_len) || G.od.len < HDR;
     G.t = p.out + G.od.off + HDR;
     G.cap = G.od.len - HDR;
     return G;

@@ -63,12 +63,12 @@ __global__ __launch_bounds__(64 * FTX_WAVES) void fragment_kernel(FragTxArgs p) 
 
     // ---- checks (workgroup-uniform): nothing is stored for a datagram that fails one
     const bool slots_ok = slots_in(first, reserved, p.n_frag);
-    bool bad = d.off > p.base_len || d.len > p.base_len - d.off || d.len < 20u || d.len > 65535u || !slots_ok;
+    bool bad = span_out(d, p.base_len) || d.len < 20u || d.len > 65535u || !slots_ok;
     const uint32_t tl = bad ? 0u : d.len - 20u;
     const bool whole = d.len <= p.mtu;                              // pico_ipv4.c:1059: frag = DF, one frame
     const SlotPlan sp = slot_plan(tl, per, p.stride, 20u, whole || tl == 0u);
     const uint32_t count = sp.count, last_pl = sp.last_pl;
-    bad = bad || reserved < count || od.off > p.out_len || od.len > p.out_len - od.off || sp.need > od.len;
+    bad = bad || reserved < count || span_out(od, p.out_len) || sp.need > od.len;
     const uint8_t* h = p.base + d.off;
     if (!bad) bad = ((uint32_t)h[0] & 0x0Fu) != 5u;
 
@@ -164,7 +164,7 @@ int pico_csum_launch_fragment(const void* base, uint64_t base_len, const void* d
                  groups, n_frag, stride, static_cast<uint8_t*>(out), out_len,
                  static_cast<const pico_csum_desc_dev*>(out_desc), static_cast<pico_csum_desc_dev*>(o_frag), o_count,
                  o_l4, verdict, flags};
-    if (n_dgram >= SHORT_GROUPS_MIN && (uint64_t)n_frag <= (uint64_t)SHORT_SLOTS_AVG * n_dgram)
+    if (short_groups(n_dgram, n_frag))
         hipLaunchKernelGGL((fragment_kernel<1u, 1u>), dim3(n_dgram), dim3(64), 0, static_cast<hipStream_t>(stream), a);
     else
         hipLaunchKernelGGL((fragment_kernel<4u, 3u>), dim3(n_dgram), dim3(256), 0, static_cast<hipStream_t>(stream), a);

@@ -2,7 +2,8 @@
 // and summed in one pass) and the notices of pico_icmp4_notify (unreachable, time exceeded,
 // parameter problem), each a finished IPv4 datagram in its own output region -- and its launcher.
 // The contract: include/pico_csum.h, pico_icmp4_reply_batch_dev.  Helpers, the 16-byte unit mover
-// (unit_pair_move) and the arithmetic contract: pico_csum_dev.h.
+// (unit_pair_move), the header word's halves and store (halves, store_word) and the arithmetic
+// contract: pico_csum_dev.h.
 //
 // Reference: pico_icmp4_process_in (modules/pico_icmp4.c:47-85: type 8 -> 0, the duplicate check on
 // its statics :61-69, pico_icmp4_checksum :30-41 over the whole transport, pico_ipv4_rebound);
@@ -23,8 +24,7 @@
 //         below): an echo's transport bytes 4 .. T move through unit_pair_move into their own
 //         member's sum (SPLIT); a notice's quote is one 32-bit word a lane.  Behind the wave's two reductions each answer's header words -- the
 //         IPv4 header, the ICMP header with its checksum, a notice's quote -- are written once,
-//         complete: a 32-bit store per word where the answer is 4-byte aligned, byte stores
-//         otherwise.  Nothing is stored for a record that is not ACCEPT.
+//         complete (store_word).  Nothing is stored for a record that is not ACCEPT.
 //   K13d  one workgroup: the batch's last echo request's (id, seq) -> the carried state.
 #include "pico_csum_dev.h"
 
@@ -53,7 +53,7 @@ __device__ __forceinline__ uint32_t icmp4_judge(const Icmp4Args& p, uint64_t i, 
     alen = 0;
     const pico_csum_desc_dev d = p.desc[i], od = p.odesc[i];
     const uint32_t type = req_type(p, i);
-    if (d.off > p.base_len || d.len > p.base_len - d.off || d.len < 20u) return V_MALFORMED;
+    if (span_out(d, p.base_len) || d.len < 20u) return V_MALFORMED;
     if (!(type == 0u || type == 3u || type == 11u || type == 12u)) return V_MALFORMED;
     const uint8_t* h = p.base + d.off;
     const uint32_t w0 = ld32(h), tot = bswap16(w0 >> 16);
@@ -69,7 +69,7 @@ __device__ __forceinline__ uint32_t icmp4_judge(const Icmp4Args& p, uint64_t i, 
         if (tot < 20u || q > d.len) return V_MALFORMED;
         need = 28u + q;
     }
-    if (od.off > p.out_len || od.len > p.out_len - od.off || need > od.len) return V_MALFORMED;
+    if (span_out(od, p.out_len) || need > od.len) return V_MALFORMED;
     alen = need;
     return V_ACCEPT;
 }
@@ -181,8 +181,6 @@ struct Icmp4Member {
     uint32_t icmp0;         // type | code << 8 (crc 0)
 };
 
-__device__ __forceinline__ uint32_t halves2(uint32_t w) { return (w & 0xFFFFu) + (w >> 16); }
-
 __device__ __forceinline__ Icmp4Member icmp4_member(const Icmp4Args& p, uint64_t i, bool exists) {
     Icmp4Member m{};
     if (!exists || uni((uint32_t)p.verdict[i]) != V_ACCEPT) return m;
@@ -216,7 +214,7 @@ __device__ __forceinline__ Icmp4Member icmp4_member(const Icmp4Args& p, uint64_t
     m.ip[2] = 64u | (1u << 8);
     m.ip[3] = r0;
     m.ip[4] = uni(ld32(m.h + 12));
-    const uint32_t crc = finalize(halves2(m.ip[0]) + halves2(m.ip[1]) + halves2(m.ip[2]) + halves2(m.ip[3]) + halves2(m.ip[4]));
+    const uint32_t crc = finalize(halves(m.ip[0]) + halves(m.ip[1]) + halves(m.ip[2]) + halves(m.ip[3]) + halves(m.ip[4]));
     m.ip[2] |= bswap16(crc) << 16;
     return m;
 }
@@ -258,7 +256,7 @@ __global__ __launch_bounds__(256) void icmp4_answer_kernel(Icmp4Args p) {
     const uint32_t wA = icmp4_word(A, lane, nbA), wB = icmp4_word(B, lane, nbB);
     // pico_icmp4_checksum: the ICMP header's words and a notice's quote here, an echo's bytes 4 .. T
     // as the mover copies them
-    uint32_t accA = lane >= 5u && nbA ? halves2(wA) : 0u, accB = lane >= 5u && nbB ? halves2(wB) : 0u;
+    uint32_t accA = lane >= 5u && nbA ? halves(wA) : 0u, accB = lane >= 5u && nbB ? halves(wB) : 0u;
     unit_pair_move<ICMP4_U, false, true>(A.s, B.s, A.echo ? A.d + 24u : 0u, B.echo ? B.d + 24u : 0u, A.e, B.e, A.pl, B.pl,
                                          B.on, lane, accA, accB);
     const uint32_t crcA = finalize(wave_total(accA));
@@ -270,12 +268,7 @@ __global__ __launch_bounds__(256) void icmp4_answer_kernel(Icmp4Args p) {
         if (nb == 0u) continue;
         uint32_t v = b ? wB : wA;
         if (lane == 5u) v |= bswap16(b ? crcB : crcA) << 16;
-        uint8_t* t = reinterpret_cast<uint8_t*>(b ? B.d : A.d) + 4u * lane;
-        if (nb == 4u && (reinterpret_cast<uint64_t>(t) & 3u) == 0u) {
-            *reinterpret_cast<uint32_t*>(t) = v;
-        } else {
-            for (uint32_t k = 0; k < nb; ++k) t[k] = (uint8_t)(v >> (8u * k));
-        }
+        store_word(reinterpret_cast<uint8_t*>(b ? B.d : A.d) + 4u * lane, v, nb);
     }
 }
 

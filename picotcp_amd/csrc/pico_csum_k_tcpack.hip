@@ -2,7 +2,8 @@
 // (pico_csum_k_tcprx.hip) that finishes the checksum verdicts the coalescing left open (TCP_OLD and
 // TCP_HELD segments: "payload not read"), and writes each connection's ready-to-send ACK frame --
 // ack number, window, options with the SACK blocks of the held segments, both checksums -- and its
-// launcher.  Helpers, the segment parse (seg_parse) and the arithmetic contract: pico_csum_dev.h.
+// launcher.  Helpers, the segment parse (seg_parse), the header word's halves and store (halves,
+// store_word) and the arithmetic contract: pico_csum_dev.h.
 // The contract: include/pico_csum.h, pico_tcp_ack_batch_dev.
 //
 // Reference: tcp_data_in_send_ack -> tcp_send_ack -> tcp_send_empty (modules/pico_tcp.c:1716-1725,
@@ -24,7 +25,7 @@
 //      next_segment: one contiguous run), computes the window and lays the
 //      frame out in LDS over the template's words;
 //   5. wave 0 takes the frame's words into registers, sums both headers there (wave_total), sets the
-//      two crc fields and stores the words.
+//      two crc fields and stores the words (store_word).
 // No library scratch, one launch, graph-capturable.  Every loop is bounded by the group's size.
 #include "pico_csum_dev.h"
 
@@ -73,10 +74,6 @@ struct TcpAckLds {
     uint32_t frame[25];             // the ACK: 40 + 60 bytes at most
     uint32_t nlist, due, nqueue, held, flen, malformed;
 };
-
-__device__ __forceinline__ uint32_t halves(uint32_t w, bool lo, bool hi) {
-    return (lo ? w & 0xFFFFu : 0u) + (hi ? w >> 16 : 0u);
-}
 
 // One wave sums the payloads of two segments A and B -- pl bytes at address s, any alignment each --
 // without storing anything.  A payload that starts r = s & 15 bytes into a 16-byte block has blocks
@@ -138,9 +135,14 @@ __global__ __launch_bounds__(64 * TAK_WAVES) void tcp_ack_kernel(TcpAckArgs p) {
 
     // ---- the connection's own checks (workgroup-uniform, in an order that never reads past the
     // template's len): nothing is written for a connection that fails one
-    const bool grp_in = first <= p.n_seg && cnt <= p.n_seg - first;
-    bool bad = cnt == 0u || cnt > TCPACK_MAX || !grp_in || (cflags & ~1u) != 0u || (ak.aflags & ~1u) != 0u;
-    bad = bad || td.off > p.tmpl_len || td.len > p.tmpl_len - td.off || td.len < 1u;
+    const auto reject = [&] {                                               // zero descriptor + MALFORMED
+        if (tid == 0) {
+            if (p.o_ack) p.o_ack[g] = pico_csum_desc_dev{0, 0, 0};
+            if (p.verdict) p.verdict[g] = (uint8_t)V_MALFORMED;
+        }
+    };
+    bool bad = cnt == 0u || cnt > TCPACK_MAX || !slots_in(first, cnt, p.n_seg) || (cflags & ~1u) != 0u || (ak.aflags & ~1u) != 0u;
+    bad = bad || span_out(td, p.tmpl_len) || td.len < 1u;
     const uint8_t* h = p.tmpl + td.off;
     uint32_t N = 20u;
     bool v6 = false;
@@ -152,14 +154,7 @@ __global__ __launch_bounds__(64 * TAK_WAVES) void tcp_ack_kernel(TcpAckArgs p) {
         if (!bad) bad = v6 ? (uint32_t)h[6] != 6u : ((b0 & 15u) != 5u || (uint32_t)h[9] != 6u);
         bad = bad || td.len < N + 20u;
     }
-    bad = bad || od.off > p.out_len || od.len > p.out_len - od.off;
-    if (bad) {
-        if (tid == 0) {
-            if (p.o_ack) p.o_ack[g] = pico_csum_desc_dev{0, 0, 0};
-            if (p.verdict) p.verdict[g] = (uint8_t)V_MALFORMED;
-        }
-        return;
-    }
+    if (bad || span_out(od, p.out_len)) return reject();
     const uint32_t rcv = rcv_nxt + p.o_len[g];                              // rcv'
 
     if (tid == 0) L.nlist = L.due = L.nqueue = L.held = L.flen = L.malformed = 0u;
@@ -356,13 +351,7 @@ __global__ __launch_bounds__(64 * TAK_WAVES) void tcp_ack_kernel(TcpAckArgs p) {
     __syncthreads();
 
     const uint32_t flen = L.flen;
-    if (L.malformed) {
-        if (tid == 0) {
-            if (p.o_ack) p.o_ack[g] = pico_csum_desc_dev{0, 0, 0};
-            if (p.verdict) p.verdict[g] = (uint8_t)V_MALFORMED;
-        }
-        return;
-    }
+    if (L.malformed) return reject();
 
     // ---- the verdicts the coalescing left open
     for (uint32_t j = tid; j < cnt; j += NT)
@@ -377,26 +366,16 @@ __global__ __launch_bounds__(64 * TAK_WAVES) void tcp_ack_kernel(TcpAckArgs p) {
         const uint32_t nw = flen >> 2, thl = flen - N;
         const uint32_t w = lane < nw ? L.frame[lane] : 0u;
         const uint32_t j = lane - tw0;                                      // the word's place in the TCP header
-        const uint32_t n_part = !v6 && lane < 5u ? halves(w, true, true) : 0u;
-        const uint32_t a_part = (v6 ? lane >= 2u && lane < 10u : lane >= 3u && lane < 5u) ? halves(w, true, true) : 0u;
-        const uint32_t t_part = lane >= tw0 && lane < nw ? halves(w, true, true) : 0u;
+        const uint32_t n_part = !v6 && lane < 5u ? halves(w) : 0u;
+        const uint32_t a_part = (v6 ? lane >= 2u && lane < 10u : lane >= 3u && lane < 5u) ? halves(w) : 0u;
+        const uint32_t t_part = lane >= tw0 && lane < nw ? halves(w) : 0u;
         const uint32_t ncrc = finalize(wave_total(n_part));
         // struct pico_ipv4_pseudo_hdr / pico_ipv6_pseudo_hdr as LE words: the addresses, proto 6, the length
         const uint32_t tcrc = finalize(wave_total(a_part + t_part) + (6u << 8) + bswap16(thl));
         uint32_t v = w;
         if (!v6 && lane == 2u) v = (v & 0xFFFFu) | (bswap16(ncrc) << 16);
         if (j == 4u) v = (v & 0xFFFF0000u) | bswap16(tcrc);
-        if (lane < nw) {
-            uint8_t* t = p.out + od.off + 4u * lane;
-            if ((reinterpret_cast<uint64_t>(t) & 3u) == 0u) {
-                *reinterpret_cast<uint32_t*>(t) = v;
-            } else {
-                t[0] = (uint8_t)v;
-                t[1] = (uint8_t)(v >> 8);
-                t[2] = (uint8_t)(v >> 16);
-                t[3] = (uint8_t)(v >> 24);
-            }
-        }
+        if (lane < nw) store_word(p.out + od.off + 4u * lane, v);
     }
 }
 
@@ -414,7 +393,7 @@ int pico_csum_launch_tcp_ack(const void* base, uint64_t base_len, const void* se
                  static_cast<const pico_csum_desc_dev*>(tmpl_desc), static_cast<const pico_csum_tcp_ack_dev*>(ack),
                  static_cast<uint8_t*>(out), out_len, static_cast<const pico_csum_desc_dev*>(out_desc),
                  static_cast<pico_csum_desc_dev*>(o_ack), verdict};
-    if (n_conn >= SHORT_GROUPS_MIN && (uint64_t)n_seg <= (uint64_t)SHORT_SLOTS_AVG * n_conn)
+    if (short_groups(n_conn, n_seg))
         hipLaunchKernelGGL(tcp_ack_kernel<1u>, dim3(n_conn), dim3(64), 0, static_cast<hipStream_t>(stream), a);
     else
         hipLaunchKernelGGL(tcp_ack_kernel<4u>, dim3(n_conn), dim3(256), 0, static_cast<hipStream_t>(stream), a);

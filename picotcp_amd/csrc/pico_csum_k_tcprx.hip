@@ -138,9 +138,8 @@ __global__ __launch_bounds__(64 * TRX_WAVES) void tcp_coalesce_kernel(TcpRxArgs 
     const uint32_t cap = od.len;
 
     // ---- the connection's own checks (workgroup-uniform): nothing of the region is written
-    const bool grp_in = first <= p.n_seg && cnt <= p.n_seg - first;
-    const bool bad = cnt == 0u || cnt > TCPRX_MAX || !grp_in || od.off > p.out_len || od.len > p.out_len - od.off ||
-                     (cflags & ~1u) != 0u;
+    const bool grp_in = slots_in(first, cnt, p.n_seg);
+    const bool bad = cnt == 0u || cnt > TCPRX_MAX || !grp_in || span_out(od, p.out_len) || (cflags & ~1u) != 0u;
     if (bad) {
         if (p.seg_verdict && grp_in)
             for (uint32_t j = tid; j < cnt; j += NT) p.seg_verdict[first + j] = (uint8_t)V_MALFORMED;
@@ -239,7 +238,7 @@ int pico_csum_launch_tcp_coalesce(const void* base, uint64_t base_len, const voi
     TcpRxArgs a{static_cast<const uint8_t*>(base), base_len, static_cast<const pico_csum_desc_dev*>(seg), n_seg, groups,
                 conn, n_conn, static_cast<uint8_t*>(out), out_len, static_cast<const pico_csum_desc_dev*>(out_desc),
                 o_len, seg_verdict, verdict};
-    if (n_conn >= SHORT_GROUPS_MIN && (uint64_t)n_seg <= (uint64_t)SHORT_SLOTS_AVG * n_conn)
+    if (short_groups(n_conn, n_seg))
         hipLaunchKernelGGL(tcp_coalesce_kernel<1u>, dim3(n_conn), dim3(64), 0, static_cast<hipStream_t>(stream), a);
     else
         hipLaunchKernelGGL(tcp_coalesce_kernel<4u>, dim3(n_conn), dim3(256), 0, static_cast<hipStream_t>(stream), a);

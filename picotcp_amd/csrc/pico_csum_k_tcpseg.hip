@@ -2,8 +2,8 @@
 // long payload per connection scattered into segment-sized frames, every frame with its own IPv4
 // header checksum and TCP checksum, in one pass that reads each payload byte once -- and its
 // launcher.  The TCP sibling of the fragmentation scatter (pico_csum_k_fragtx.hip), whose output
-// conventions it keeps.  Helpers, the 16-byte unit mover both go through (unit_pair_move) and the
-// arithmetic contract: pico_csum_dev.h.
+// conventions it keeps.  Helpers, the 16-byte unit mover both go through (unit_pair_move), the header
+// word's halves and store (halves, store_word) and the arithmetic contract: pico_csum_dev.h.
 //
 // Reference: pico_socket_xmit (stack/pico_socket.c:1322-1358) loops pico_socket_xmit_one
 // (:1070-1127: a frame per `space` bytes, memcpy of the payload); pico_tcp_push
@@ -26,8 +26,7 @@
 //   3. behind the reductions the wave writes both headers once, complete: the template's words
 //      with len, id + k, DF and pico_ipv4_checksum (IPv4) or the payload length (IPv6), seq +
 //      k per, and pico_tcp_checksum = the template's sums + the segment's own len / seq words + its
-//      payload sum.  A 32-bit store per word where the frame is 4-byte aligned, byte stores
-//      otherwise.
+//      payload sum (store_word).
 #include "pico_csum_dev.h"
 
 namespace {
@@ -55,10 +54,6 @@ struct TcpSegArgs {
 // point, 29360 streams of 7 segments.
 constexpr uint32_t TCPSEG_SHORT_U = 1u;
 
-__device__ __forceinline__ uint32_t halves(uint32_t w, bool lo, bool hi) {
-    return (lo ? w & 0xFFFFu : 0u) + (hi ? w >> 16 : 0u);
-}
-
 // TSG_WAVES waves per stream, TSG_U 64-unit rows per step (3: two 1448-byte payloads)
 template <uint32_t TSG_WAVES, uint32_t TSG_U>
 __global__ __launch_bounds__(64 * TSG_WAVES) void tcp_segment_kernel(TcpSegArgs p) {
@@ -72,7 +67,7 @@ __global__ __launch_bounds__(64 * TSG_WAVES) void tcp_segment_kernel(TcpSegArgs 
     // ---- checks (workgroup-uniform, in an order that never reads past d.len): nothing is stored
     // for a stream that fails one
     const bool slots_ok = slots_in(first, reserved, p.n_seg);
-    bool bad = d.off > p.base_len || d.len > p.base_len - d.off || d.len < 1u;
+    bool bad = span_out(d, p.base_len) || d.len < 1u;
     const uint8_t* h = p.base + d.off;
     uint32_t N = 20u, thl = 20u;
     bool v6 = false;
@@ -95,7 +90,7 @@ __global__ __launch_bounds__(64 * TSG_WAVES) void tcp_segment_kernel(TcpSegArgs 
     bad = bad || (uint64_t)(v6 ? thl : H) + seg0 > 65535u || (uint64_t)H + seg0 > p.stride;
     const SlotPlan sp = bad ? SlotPlan{0u, 0u, 0u} : slot_plan(P, per, p.stride, H, P <= per);
     const uint32_t count = sp.count, last_pl = sp.last_pl;
-    bad = bad || reserved < count || !slots_ok || od.off > p.out_len || od.len > p.out_len - od.off || sp.need > od.len;
+    bad = bad || reserved < count || !slots_ok || span_out(od, p.out_len) || sp.need > od.len;
 
     if (p.o_seg && slots_ok)
         write_slots(p.o_seg + first, reserved, bad ? 0u : count, od.off, p.stride, H, per, last_pl, tid, 64u * TSG_WAVES);
@@ -112,7 +107,7 @@ __global__ __launch_bounds__(64 * TSG_WAVES) void tcp_segment_kernel(TcpSegArgs 
     const uint32_t j = lane - tw0;                                  // the word's place in the TCP header
     // IPv4 header without len (word 0 high), id / frag (word 1), crc (word 2 high)
     const uint32_t n_part = !v6 && lane < 5u ? halves(tw, lane != 1u, lane >= 3u) : 0u;
-    const uint32_t a_part = (v6 ? lane >= 2u && lane < 10u : lane >= 3u && lane < 5u) ? halves(tw, true, true) : 0u;
+    const uint32_t a_part = (v6 ? lane >= 2u && lane < 10u : lane >= 3u && lane < 5u) ? halves(tw) : 0u;
     // TCP header without seq (word 1) and crc (word 4 low)
     const uint32_t t_part = lane >= tw0 && lane < nw ? halves(tw, j != 1u && j != 4u, j != 1u) : 0u;
     const uint32_t nsum = wave_total(n_part);
@@ -160,15 +155,7 @@ __global__ __launch_bounds__(64 * TSG_WAVES) void tcp_segment_kernel(TcpSegArgs 
                 }
                 v = j == 1u ? __builtin_bswap32(seq) : v;
                 v = j == 4u ? (v & 0xFFFF0000u) | bswap16(tcrc) : v;
-                uint8_t* t = reinterpret_cast<uint8_t*>(b ? dB : dA) + 4u * lane;
-                if ((reinterpret_cast<uint64_t>(t) & 3u) == 0u) {
-                    *reinterpret_cast<uint32_t*>(t) = v;
-                } else {
-                    t[0] = (uint8_t)v;
-                    t[1] = (uint8_t)(v >> 8);
-                    t[2] = (uint8_t)(v >> 16);
-                    t[3] = (uint8_t)(v >> 24);
-                }
+                store_word(reinterpret_cast<uint8_t*>(b ? dB : dA) + 4u * lane, v);
             }
         }
     }
@@ -186,7 +173,7 @@ int pico_csum_launch_tcp_segment(const void* base, uint64_t base_len, const void
                  groups, n_seg, stride, static_cast<uint8_t*>(out), out_len,
                  static_cast<const pico_csum_desc_dev*>(out_desc), static_cast<pico_csum_desc_dev*>(o_seg), o_count,
                  verdict};
-    if (n_stream >= SHORT_GROUPS_MIN && (uint64_t)n_seg <= (uint64_t)SHORT_SLOTS_AVG * n_stream)
+    if (short_groups(n_stream, n_seg))
         hipLaunchKernelGGL((tcp_segment_kernel<1u, TCPSEG_SHORT_U>), dim3(n_stream), dim3(64), 0,
                            static_cast<hipStream_t>(stream), a);
     else

@@ -504,15 +504,16 @@ def tcpseg_count(payload: int, per: int) -> int:
     return max(1, -(-payload // per))
 
 
-def tcp_streams(lengths, family=4, thl=20, per=1448, stride: int = 1504, seed: int = 51, align=0, out_off: int = 12,
+def tcp_streams(lengths, family=4, thl=20, per=1448, stride: int = 1504, seed: int = 51, align=0, out_off=12,
                 spare: int = 0, seq=None, ident=None):
     """Send units for pico_tcp_segment_batch_dev: per stream a network header (family 4: IPv4, IHL 5;
     6: IPv6, no extension header), a TCP header of `thl` bytes (PSH|ACK, options arbitrary) and
     `lengths[g]` payload bytes, contiguous; the fields the batch does not read (IPv4 len / frag /
     crc, IPv6 payload length, TCP crc) are arbitrary.  family, thl, per, align (the header's address
     mod 16 in the buffer), seq and ident (template seq / IPv4 id; random when None): one value or one
-    per stream.  Output regions are laid out back to back, each starting at out_off mod 16 and
-    holding exactly the segments at `stride`; every group reserves its segment count + `spare` slots.
+    per stream.  Output regions are laid out back to back, each starting at out_off mod 16 (one value
+    or one per stream) and holding exactly the segments at `stride`; every group reserves its segment
+    count + `spare` slots.
     Returns (buffer, stream offsets uint64, stream bytes uint32, per uint32[n], groups uint32[n, 2] =
     (first slot, slots reserved), out offsets uint64, out capacities uint32, n_seg, out_len)."""
     lengths = np.asarray(lengths, dtype=np.int64)
@@ -556,10 +557,11 @@ def tcp_streams(lengths, family=4, thl=20, per=1448, stride: int = 1504, seed: i
     groups = np.stack([first, reserved], axis=1).astype(np.uint32)
     last = hl + lengths - (cnt - 1) * pers.astype(np.int64)
     cap = ((cnt - 1) * stride + last).astype(np.uint32)
+    ooffs = np.broadcast_to(np.asarray(out_off, dtype=np.int64), (n,))
     ooff = np.zeros(n, np.uint64)
     pos = 0
     for g in range(n):
-        pos += (out_off - pos) % 16
+        pos += (int(ooffs[g]) - pos) % 16
         ooff[g] = pos
         pos += int(cap[g])
     return buf, off, (hl + lengths).astype(np.uint32), pers, groups, ooff, cap, int(reserved.sum()), pos + 16
@@ -681,14 +683,15 @@ def tcp_rx_bursts(n_conn: int, seed: int = 83, family=4, thl=32, per=1448, max_b
     return conns, streams
 
 
-def tcp_ack_inputs(conns, seed: int = 89, space=16384, ts_ok=None, region: int = 100, out_off: int = 0, align=0):
+def tcp_ack_inputs(conns, seed: int = 89, space=16384, ts_ok=None, region: int = 100, out_off=0, align=0):
     """What pico_tcp_ack_batch_dev takes beside the coalescing's arrays, for `conns` (tcp_rx_bursts' /
     tcp_rx_pack's list): per connection a header template answering its first frame -- the network
     header with the addresses swapped (IPv4: IHL 5, its own id, ttl 64; IPv6: no extension header) and
     a 20-byte TCP header with the ports swapped, a random seq (snd_nxt) and random bytes in the fields
     the batch does not read -- at `align` mod 16 (one value or one per connection), and a
     pico_csum_tcp_ack record (space: one value or one per connection; ts_ok: likewise, None = seeded).
-    Output regions of `region` bytes back to back, each at out_off mod 16.  Returns (template buffer,
+    Output regions of `region` bytes back to back, each at out_off mod 16 (one value or one per
+    connection).  Returns (template buffer,
     template offsets uint64, template bytes uint32, ack records as a structured array (space, tsval,
     tsecr, aflags), out offsets uint64, out capacities uint32, out_len)."""
     rng = np.random.default_rng(seed)
@@ -723,10 +726,11 @@ def tcp_ack_inputs(conns, seed: int = 89, space=16384, ts_ok=None, region: int =
     buf = random_bytes(seed ^ 0x51C3, pos + 16)
     for g in range(n):
         buf[int(off[g]):int(off[g]) + pieces[g].size] = pieces[g]
+    ooffs = np.broadcast_to(np.asarray(out_off, dtype=np.int64), (n,))
     ooff = np.zeros(n, np.uint64)
     pos = 0
     for g in range(n):
-        pos += (out_off - pos) % 16
+        pos += (int(ooffs[g]) - pos) % 16
         ooff[g] = pos
         pos += region
     return buf, off, ln, ack, ooff, np.full(n, region, np.uint32), pos + 16
