@@ -61,7 +61,8 @@ extern "C" {
  *      and the PICO_CSUM_FLOW_* modes -- likewise;
  *   4 (added, no bump): pico_tcp_ack_batch_dev and struct pico_csum_tcp_ack -- likewise;
  *   4 (added, no bump): pico_icmp4_reply_batch_dev, struct pico_csum_icmp4_req and struct
- *      pico_csum_icmp4_state -- likewise. */
+ *      pico_csum_icmp4_state -- likewise;
+ *   4 (added, no bump): pico_icmp6_reply_batch_dev and struct pico_csum_icmp6_req -- likewise. */
 #define PICO_CSUM_ABI_VERSION 4
 
 /* picoTCP pico_err values used here (include/pico_protocol.h:27,31,38 + ENODEV) */
@@ -730,6 +731,83 @@ struct pico_csum_icmp4_req {   /* 8 bytes, per record, host-filled */
 struct pico_csum_icmp4_state { uint32_t seen; uint16_t id, seq; };   /* process_in's statics: firstpkt, last_id, last_seq */
 int pico_icmp4_reply_batch_dev(const void *d_base, uint64_t base_len, const struct pico_csum_desc *d_desc, uint32_t n,
                                const struct pico_csum_icmp4_req *d_req, struct pico_csum_icmp4_state *d_state,
+                               void *d_out, uint64_t out_len, const struct pico_csum_desc *d_out_desc,
+                               struct pico_csum_desc *d_out_ans, uint8_t *d_verdict, uint32_t flags, void *stream);
+
+/* A burst's ICMPv6 answers, the IPv6 twin of the batch above: the echo replies and the notices (destination
+ * unreachable, packet too big, time exceeded, parameter problem), each built on the device as a finished
+ * IPv6 datagram in its own output region.  The batch form of pico_icmp6_process_in /
+ * pico_icmp6_send_echoreply (modules/pico_icmp6.c:94-133, :61-92) with pico_icmp6_checksum (:38-55) and
+ * pico_ipv6_frame_push (modules/pico_ipv6.c:1324-1339, the header :1283-1322), and of pico_icmp6_notify
+ * (modules/pico_icmp6.c:153-227) behind its wrappers (:229-293).  The IPv6 answers are the heavier ones: the
+ * checksum covers a 40-byte pseudo header, and a notice quotes up to 1232 bytes of the datagram, copied and
+ * summed, where an ICMPv4 notice quotes 28.  There is NO state argument: the reference keeps none for
+ * ICMPv6 -- pico_icmp6_process_in has no duplicate statics, and the compiled stack answers the same
+ * (id, seq) every time it arrives (tests/golden/ref_icmp6_cases.npz).  The host chooses which datagram gets
+ * which record, looks up the route (src), limits the rate and keeps the ping client.
+ *   d_desc[i]  the datagram that is answered: desc.off -> its IPv6 header, desc.len = bytes available from
+ *              there (nothing past it or past base_len contributes; reads follow the whole-16-byte-block
+ *              rule above); desc.seed is not read.
+ *   d_req[i]   struct pico_csum_icmp6_req, host-filled: src = the answer's source where the rules below call
+ *              for it (the address of the link the route to the asker uses), hop = the answer's hop limit
+ *              (the device's hostvars.hoplimit), type 0 = answer as pico_icmp6_process_in does, type 1 / 2 /
+ *              3 / 4 with any code = the notice to send, arg = type 4's pointer or type 2's MTU (host order).
+ *   d_out_desc[i]  the answer's region in d_out (off any alignment, len = capacity).
+ *   d_out_ans[i]   {the answer's offset in d_out, its length, 0} -- with d_out, the input of the TX path or of
+ *              pico_ipv6_checksum_batch_dev as it is -- or {0, 0, 0}.
+ * Echo (type 0).  A record parses when its version is 6, 40 + payload-length field <= desc.len and the
+ * extension-header walk stays inside the payload -- the IPv6 RX batch's walk (hop-by-hop 0, routing 43,
+ * destination options 60; pico_ipv6_extension_headers, modules/pico_ipv6.c:707-809, with the sequence check
+ * before it).  It is an echo request when the walk ends at next header 58 with at least 8 transport bytes
+ * and ICMPv6 type 128.  A walk that ends at 58 with another type, at a fragment header, at any other
+ * protocol or at a header the reference discards is V_UNTOUCHED and nothing is written: neighbour
+ * discovery, MLD, echo replies and unreachables stay the host's (:104-131).  An infeasible length (a walk
+ * that would leave the payload, fewer than 8 transport bytes) is V_MALFORMED.
+ *   the answer  40 + T bytes, T = payload-length field - the extension headers' bytes: 60 00 00 00, len T,
+ *              nxthdr 58, req.hop, src = the request's destination -- unless its first byte is 0xff: then
+ *              req.src (ipv6_push_hdr_adjust, :1283-1289: a multicast source is replaced by the link's
+ *              address) --, dst = the request's source; then 81 00, crc, the request's transport bytes
+ *              4 .. T.  crc = pico_icmp6_checksum over the pseudo header (src, dst, T, 58) and the bytes AS
+ *              COPIED -- never derived from the request's crc: the reference answers a corrupted request
+ *              with a valid reply.  The answer never carries the request's extension headers (the reply is
+ *              a freshly allocated frame, :68).
+ * Notices (type 1, 3, 4; any code): pico_icmp6_notify literally.  Only the payload-length field is parsed.
+ * q = min(40 + payload-length field, 1232) bytes are quoted from the IPv6 header on as they lie.  The answer
+ * is 48 + q bytes: the header as above with src = req.src and dst = the datagram's source; type, code, crc;
+ * one 32-bit word -- 0 for types 1 and 3, long_be(req.arg) for type 4 --; the quote.  Types 1 and 3 are not
+ * sent when the datagram's destination is multicast (first byte 0xff; the wrappers :229-293 return 0):
+ * V_UNTOUCHED, nothing written.  Type 4 is sent regardless (:281-284).
+ * Packet Too Big (type 2) -- documented difference (2) below: the layout of the other notices, the word =
+ * long_be(req.arg), the MTU; code 0 whatever req.code says; the multicast rule of type 1.
+ *   d_verdict[i]  ACCEPT = the answer is written and d_out_ans[i] set; V_UNTOUCHED as above; MALFORMED =
+ *              nothing of the region is written: a descriptor past base_len or of fewer than 40 bytes, a
+ *              req.type outside {0, 1, 2, 3, 4} or req.rsvd != 0, an echo record that fails the parse, a
+ *              notice with q > desc.len, and -- for a record that would be answered -- a region past out_len
+ *              or smaller than the answer.  For both d_out_ans[i] = {0, 0, 0}.
+ * No byte outside a region is written, and inside it only the answer's own bytes.  Regions must not overlap.
+ * Documented differences from the reference: (1) the reference takes an echo's T from the frame's length
+ * (:110), so bytes behind the datagram (padding, a trailer) are echoed; the batch stops at the datagram's
+ * end, as the ICMPv4 batch does.  (2) pico_icmp6_pkt_too_big calls pico_icmp6_notify with a type its switch
+ * does not handle (:217-218, :271), so the reference sends nothing; the batch states the evident intent, as
+ * the ICMPv4 batch does for options.
+ * Out of scope: neighbour advertisements are not built (the reference harness captures none; a later
+ * addition can take them as type 136); rate limiting, the route lookup and the choice of records stay with
+ * the host.
+ * Host checks, -EINVAL before any launch: a NULL required pointer (all but d_out_ans); d_desc, d_out_desc or
+ * d_out_ans not 16-byte aligned; d_req not 4-byte aligned; flags != 0 (reserved).  n == 0 is a no-op;
+ * without a device -ENODEV.  Two launches on one stream (verdicts; one wave per two records for the answers,
+ * per record when base_len >= 1024 n), no allocation, no library scratch, no spin-wait, no host
+ * synchronisation: capturable behind the batch whose verdicts chose the records.  Results never depend on
+ * the launch shape. */
+struct pico_csum_icmp6_req {   /* 24 bytes, per record, host-filled */
+    uint8_t  src[16];          /* the answer's source where the rules above call for it */
+    uint32_t arg;              /* host order: type 4 the pointer, type 2 the MTU; not read for 0 / 1 / 3 */
+    uint8_t  type, code;       /* type 0: answer as pico_icmp6_process_in does (echo); 1 / 2 / 3 / 4: the notice */
+    uint8_t  hop;              /* the answer's hop limit: the device's hostvars.hoplimit */
+    uint8_t  rsvd;             /* must be 0 */
+};
+int pico_icmp6_reply_batch_dev(const void *d_base, uint64_t base_len, const struct pico_csum_desc *d_desc, uint32_t n,
+                               const struct pico_csum_icmp6_req *d_req,
                                void *d_out, uint64_t out_len, const struct pico_csum_desc *d_out_desc,
                                struct pico_csum_desc *d_out_ans, uint8_t *d_verdict, uint32_t flags, void *stream);
 

@@ -37,6 +37,7 @@ EXPORTED = (
     "pico_tcp_coalesce_batch_dev",
     "pico_tcp_ack_batch_dev",
     "pico_icmp4_reply_batch_dev",
+    "pico_icmp6_reply_batch_dev",
     "pico_flow_group_scratch_bytes",
     "pico_flow_group_batch_dev",
     "pico_csum_ctx_create",
@@ -65,7 +66,7 @@ V_ACCEPT, V_NET_BAD, V_L4_BAD, V_MALFORMED, V_EXPIRED = 1, 2, 4, 8, 16
 V_FRAG = 16                # RX / TX batches (V_EXPIRED: the forwarding batch)
 ABI_VERSION = 4
 V_DROP_L2, V_ARP, V_IPV6 = 32, 64, 128
-V_UNTOUCHED = 32            # NAT batch (same bit as V_DROP_L2)
+V_UNTOUCHED = 32            # NAT batch (same bit as V_DROP_L2); the ICMPv4 / ICMPv6 answers too
 V_LOCAL_SRC, V_DUPLICATE = 32, 64   # forwarding batch (same bits as V_DROP_L2 / V_ARP); V_DUPLICATE: the ICMPv4 answers too
 V_TCP_CTRL, V_TCP_OLD, V_TCP_HELD = 32, 64, 128   # TCP coalescing batch (same bits as V_DROP_L2 / V_ARP / V_IPV6)
 FLOW_TCP, FLOW_FRAG4, FLOW_FRAG6, FLOW_F_ETH = 1, 2, 3, 0x10   # pico_flow_group_batch_dev's mode_flags
@@ -122,6 +123,8 @@ def load() -> ctypes.CDLL:
             u32, vp)
     if hasattr(lib, "pico_icmp4_reply_batch_dev"):       # (likewise)
         sig("pico_icmp4_reply_batch_dev", ctypes.c_int, vp, u64, vp, u32, vp, vp, vp, u64, vp, vp, vp, u32, vp)
+    if hasattr(lib, "pico_icmp6_reply_batch_dev"):       # (likewise)
+        sig("pico_icmp6_reply_batch_dev", ctypes.c_int, vp, u64, vp, u32, vp, vp, u64, vp, vp, vp, u32, vp)
     if hasattr(lib, "pico_flow_group_batch_dev"):        # (an A/B build of an older round lacks it)
         sig("pico_flow_group_scratch_bytes", u64, u32, u32)
         sig("pico_flow_group_batch_dev", ctypes.c_int, vp, u64, vp, u32, vp, u32, vp, u32, u32, vp, vp, vp, vp, vp, u64, vp)

@@ -533,6 +533,51 @@ def icmp4_reply_batch(base: torch.Tensor, desc: torch.Tensor, n: int, req: torch
     return v, oa
 
 
+# struct pico_csum_icmp6_req (include/pico_csum.h): the ICMPv6 answers' per-record request
+ICMP6_REQ_DTYPE = np.dtype([("src", "u1", 16), ("arg", "<u4"), ("type", "u1"), ("code", "u1"), ("hop", "u1"), ("rsvd", "u1")])
+assert ICMP6_REQ_DTYPE.itemsize == 24
+
+
+def icmp6_reply_batch(base: torch.Tensor, desc: torch.Tensor, n: int, req: torch.Tensor, out: torch.Tensor,
+                      out_desc: torch.Tensor, flags: int = 0, stream=None, results=None):
+    """A burst's ICMPv6 answers (pico_icmp6_process_in / pico_icmp6_send_echoreply, pico_icmp6.c:94-133, :61-92,
+    with pico_icmp6_checksum :38-55 and pico_ipv6_frame_push, pico_ipv6.c:1324-1339; pico_icmp6_notify,
+    pico_icmp6.c:153-227): desc = one answered datagram per descriptor (off -> its IPv6 header, len = bytes
+    available), req = ICMP6_REQ_DTYPE records (uint8 / int32 tensor of 24 bytes a record: the answer's source,
+    type 4's pointer / type 2's MTU, type 0 = echo reply to an echo request, 1 / 2 / 3 / 4 + code = that
+    notice, the hop limit), out = uint8 device buffer, out_desc[i] = the answer's region (off, capacity).
+    There is no state: the reference keeps none for ICMPv6, repeats are answered.  flags: reserved, 0.
+    Returns (verdict uint8[n]: V_ACCEPT, V_UNTOUCHED or V_MALFORMED; out_ans uint8[16 n] = the answers'
+    descriptors, {0, 0, 0} where none was written); `results` may pass that pair preallocated, out_ans None
+    to skip it."""
+    dev = _on_batch_device(base, desc=desc, req=req, out=out, out_desc=out_desc)
+    _require_u8(base, "base")
+    _require_u8(out, "out")
+    if n < 0:
+        raise ValueError(f"n = {n}")
+    _desc_bytes(desc, n, "desc")
+    _desc_bytes(out_desc, n, "out_desc")
+    if not req.is_contiguous() or req.numel() * req.element_size() < 24 * n:
+        raise ValueError(f"req must be a contiguous tensor of {n} 24-byte records")
+    if flags != 0:
+        raise ValueError(f"flags = {flags:#x}: none is defined for this batch")
+    if results is not None and results[0] is None:
+        raise ValueError("verdict is required: the launches hand their work on through it")
+    v, oa = _results(results, _ICMP4_OUTS, (n, 16 * n), dev)
+    # the library's alignment rules (a view into a larger tensor may break them), stated before it is reached
+    for name, t, align in (("desc", desc, 16), ("out_desc", out_desc, 16), ("out_ans", oa, 16), ("req", req, 4)):
+        if t is not None and t.data_ptr() % align:
+            raise ValueError(f"{name} must be {align}-byte aligned")
+    lib = _lib.load()
+    _lib.check("pico_icmp6_reply_batch_dev",
+               lib.pico_icmp6_reply_batch_dev(_ptr(base), base.numel(), _ptr(desc), n, _ptr(req), _ptr(out), out.numel(),
+                                              _ptr(out_desc), _ptr(oa), _ptr(v), flags, _stream_handle(stream)))
+    return v, oa
+
+
+icmp6_reply = icmp6_reply_batch
+
+
 # struct pico_csum_flow_key (include/pico_csum.h): one entry of the flow grouping's connection table
 FLOW_KEY_DTYPE = np.dtype([("src", "u1", 16), ("dst", "u1", 16), ("sport", "<u2"), ("dport", "<u2"), ("family", "u1"),
                            ("reserved", "u1", 3)])

@@ -9,7 +9,7 @@
  *          every descriptor batch and the forwarding step; pico_csum_k_frag.hip:
  *          reassembly; pico_csum_k_fragtx.hip: TX fragmentation; pico_csum_k_tcpseg.hip: TCP send
  *          segmentation; pico_csum_k_tcprx.hip: TCP receive coalescing; pico_csum_k_tcpack.hip: the burst's ACKs;
- *          pico_csum_k_icmp.hip: ICMPv4 answers), reached through the thin extern "C" launchers declared below.
+ *          pico_csum_k_icmp.hip: ICMPv4 answers, pico_csum_k_icmp6.hip: ICMPv6 answers), reached through the thin extern "C" launchers declared below.
  * Layer 3: host-resident batches: pinned staging, two streams, chunked
  *          H2D -> kernel -> D2H overlap.
  */
@@ -66,6 +66,9 @@ int pico_csum_launch_tcp_ack(const void *base, uint64_t base_len, const void *se
 int pico_csum_launch_icmp4_reply(const void *base, uint64_t base_len, const void *desc, uint32_t n, const void *req,
                                  void *state, void *out, uint64_t out_len, const void *out_desc, void *o_ans,
                                  uint8_t *verdict, void *stream);
+int pico_csum_launch_icmp6_reply(const void *base, uint64_t base_len, const void *desc, uint32_t n, const void *req,
+                                 void *out, uint64_t out_len, const void *out_desc, void *o_ans, uint8_t *verdict,
+                                 void *stream);
 int pico_csum_launch_flow_group(const void *base, uint64_t base_len, const void *desc, uint32_t n,
                                 const uint8_t *verdict_in, uint32_t mode_flags, const void *known, uint32_t n_known,
                                 uint32_t seed, void *o_desc, uint32_t *o_index, uint32_t *o_groups, uint32_t *o_counts,
@@ -753,6 +756,29 @@ int pico_icmp4_reply_batch_dev(const void *d_base, uint64_t base_len, const stru
     return launch_status(pico_csum_launch_icmp4_reply(d_base, base_len, d_desc, n, d_req, d_state, d_out, out_len,
                                                       d_out_desc, d_out_ans, d_verdict, stream),
                          "pico_icmp4_reply_batch_dev");
+}
+
+int pico_icmp6_reply_batch_dev(const void *d_base, uint64_t base_len, const struct pico_csum_desc *d_desc, uint32_t n,
+                               const struct pico_csum_icmp6_req *d_req, void *d_out, uint64_t out_len,
+                               const struct pico_csum_desc *d_out_desc, struct pico_csum_desc *d_out_ans,
+                               uint8_t *d_verdict, uint32_t flags, void *stream)
+{
+    int rc;
+    if (n == 0)
+        return 0;
+    if (!d_base || !d_desc || !d_req || !d_out || !d_out_desc || !d_verdict)
+        return fail(PICO_CSUM_EINVAL, "NULL buffer (d_verdict is required)");
+    if (((uintptr_t)d_desc & 15u) != 0 || ((uintptr_t)d_out_desc & 15u) != 0 || ((uintptr_t)d_out_ans & 15u) != 0)
+        return fail(PICO_CSUM_EINVAL, "descriptor arrays must be 16-byte aligned");
+    if (((uintptr_t)d_req & 3u) != 0)
+        return fail(PICO_CSUM_EINVAL, "d_req must be 4-byte aligned");
+    if (flags != 0)
+        return fail(PICO_CSUM_EINVAL, "unknown flags 0x%x%s (none is defined for this batch)", flags, retired_note(flags));
+    if ((rc = need_device()) != 0)
+        return rc;
+    return launch_status(pico_csum_launch_icmp6_reply(d_base, base_len, d_desc, n, d_req, d_out, out_len, d_out_desc,
+                                                      d_out_ans, d_verdict, stream),
+                         "pico_icmp6_reply_batch_dev");
 }
 
 /* The flow grouping's scratch, section by section (each a multiple of 16 bytes): lay[0..6] = the byte

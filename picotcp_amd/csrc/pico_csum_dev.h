@@ -1,14 +1,14 @@
 // pico_csum_dev.h -- device helpers shared by the gfx950 kernel TUs of libpicocsum
 // (pico_csum_k_raw.hip, pico_csum_k_sorted.hip, pico_csum_k_frag.hip, pico_csum_k_fragtx.hip,
 // pico_csum_k_tcpseg.hip, pico_csum_k_tcprx.hip, pico_csum_k_tcpack.hip, pico_csum_k_icmp.hip,
-// pico_csum_k_flow.hip).
+// pico_csum_k_icmp6.hip, pico_csum_k_flow.hip).
 // Header-only, internal; everything lives in an anonymous namespace (one copy per TU).
 // In order: the checksum arithmetic and the lane-group sums (every TU); windowed buffer loads
 // (_k_raw, _k_sorted, _k_frag); the IPv4 header rules (_k_sorted, _k_tcprx); the IPv6 extension-header
-// walk (_k_sorted, _k_frag, _k_flow); the 16-byte unit mover and the output-slot rules of the scatter /
-// gather batches (_k_fragtx, _k_tcpseg, _k_tcprx; the mover: _k_icmp too); the frames written by the
+// walk (_k_sorted, _k_frag, _k_flow, _k_icmp6); the 16-byte unit mover and the output-slot rules of the scatter /
+// gather batches (_k_fragtx, _k_tcpseg, _k_tcprx; the mover: _k_icmp and _k_icmp6 too); the frames written by the
 // device: the descriptor-inside-buffer rule (_k_frag and every batch of K8-K10, K12, K13), the header
-// word's halves and store (_k_tcpseg, _k_tcpack, _k_icmp); the received TCP segment's parse (_k_tcprx, _k_tcpack); the launch-shape thresholds
+// word's halves and store (_k_tcpseg, _k_tcpack, _k_icmp, _k_icmp6); the received TCP segment's parse (_k_tcprx, _k_tcpack); the launch-shape thresholds
 // and their decision (_k_fragtx, _k_tcpseg, _k_tcprx, _k_tcpack); the dispatch shapes.
 //
 // The kernels of picoTCP's Internet checksum.
@@ -559,8 +559,9 @@ __device__ __forceinline__ uint32_t wave_total(uint32_t x) {
 //   * One byte-unaligned 16-byte load per unit, at s - o + 16 u: the source / destination shift
 //     differs from member to member.  Unit 0's load starts up to 15 bytes before the payload; the
 //     callers' payloads lie at least 20 bytes (K8: the IPv4 header), 24 bytes (K13: that and the
-//     ICMP header's first word) or 40 bytes (K9, K10: network and TCP header) into their own
-//     readable buffer, so that is its byte 5 / 9 / 25 or later.
+//     ICMP header's first word), 16 bytes (K14's notices: the quote's first 16 bytes stay on the
+//     lanes; its echoes 48) or 40 bytes (K9, K10: network and TCP header) into their own readable
+//     buffer, so that is its byte 5 / 9 / 1 / 25 or later.
 //   * e = the end of the last 16-byte block that overlaps the member's readable buffer.  The whole-
 //     block read rule of include/pico_csum.h makes [.., e) readable and nothing behind it, so the
 //     one unit whose 16 bytes would run past e is read byte by byte, its [lo, hi) only.
@@ -669,18 +670,18 @@ __device__ __forceinline__ void write_slots(pico_csum_desc_dev* slot, uint32_t r
 
 // ---------------------------------------------------------------- frames written by the device (K9, K12, K13)
 //
-// What pico_csum_k_tcpseg.hip, pico_csum_k_tcpack.hip and pico_csum_k_icmp.hip share: a lane per 32-bit
+// What pico_csum_k_tcpseg.hip, pico_csum_k_tcpack.hip, pico_csum_k_icmp.hip and pico_csum_k_icmp6.hip share: a lane per 32-bit
 // header word, its halves summed and the word stored.  The TCP/IP template's check and word sums stay in
 // _k_tcpseg and _k_tcpack, each its own: a shared check cost both kernels 4-6 % where the per-group work
 // dominates (profiles/header_words/ab_variants.txt).
 
 // Descriptor d does NOT lie inside a buffer of L bytes: THE rule for every descriptor a batch takes --
 // input, template, output region -- in seg_parse, _k_frag, _k_fragtx, _k_tcpseg, _k_tcprx, _k_tcpack and
-// _k_icmp; a new batch uses it too.  Only _k_flow spells it out (net_region): with the helper its device
+// _k_icmp, _k_icmp6; a new batch uses it too.  Only _k_flow spells it out (net_region): with the helper its device
 // code differed from the tuned text; _k_raw and _k_sorted test loose (off, len) pairs, not descriptors.
 __device__ __forceinline__ bool span_out(const pico_csum_desc_dev& d, uint64_t L) { return d.off > L || d.len > L - d.off; }
 
-// The 16-bit halves of header word w that enter a sum (_k_tcpseg, _k_tcpack, _k_icmp).
+// The 16-bit halves of header word w that enter a sum (_k_tcpseg, _k_tcpack, _k_icmp, _k_icmp6).
 __device__ __forceinline__ uint32_t halves(uint32_t w, bool lo = true, bool hi = true) {
     return (lo ? w & 0xFFFFu : 0u) + (hi ? w >> 16 : 0u);
 }

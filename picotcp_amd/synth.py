@@ -813,6 +813,105 @@ def icmp4_burst(dgrams, types, codes=0, seed: int = 97, align=0, slack=0, out_of
     return buf, off, ln, req, ooff, cap, pos + 16
 
 
+def _csum16_v6(src, dst, nxt: int, t: np.ndarray) -> int:
+    """The Internet checksum of transport t behind the IPv6 pseudo header (src, dst, long_be(len), 0 0 0, nxt)."""
+    ps = np.concatenate([np.asarray(src, np.uint8), np.asarray(dst, np.uint8),
+                         np.frombuffer(int(t.size).to_bytes(4, "big") + bytes([0, 0, 0, nxt]), np.uint8)])
+    return _csum16(np.concatenate([ps, t]))             # (the 40 pseudo bytes keep t's 16-bit pairing)
+
+
+def ipv6_datagram(rng, nxt: int, transport: np.ndarray, src=None, dst=None, hbh: bool = False, hop: int = 64,
+                  ext: bytes = b"", first: int | None = None) -> np.ndarray:
+    """One IPv6 datagram: the 40-byte header, an 8-byte hop-by-hop header (PadN) when `hbh` -- or the raw
+    extension headers `ext`, the fixed header naming `first` as its next one --, then `transport` as it is."""
+    if hbh:
+        ext, first = bytes([nxt, 0, 1, 4, 0, 0, 0, 0]), 0
+    f = np.zeros(40 + len(ext) + transport.size, np.uint8)
+    f[0] = 0x60
+    f[1:4] = rng.integers(0, 256, 3, dtype=np.uint8) & np.array([0x0F, 0xFF, 0xFF], np.uint8)
+    f[4], f[5] = (f.size - 40) >> 8, (f.size - 40) & 0xFF
+    f[6], f[7] = (nxt if first is None else first), hop
+    for k, a in ((8, src), (24, dst)):
+        f[k:k + 16] = rng.integers(0, 256, 16, dtype=np.uint8) if a is None else np.frombuffer(bytes(a), np.uint8)
+        if a is None:
+            f[k] = 0x20                                   # (global unicast: never multicast by chance)
+    f[40:40 + len(ext)] = np.frombuffer(bytes(ext), np.uint8)
+    f[40 + len(ext):] = transport
+    return f
+
+
+def icmp6_echo_request(rng, T: int, ident: int = 0, seq: int = 0, src=None, dst=None, hbh: bool = False,
+                       icmp_type: int = 128, bad_crc: bool = False) -> np.ndarray:
+    """One IPv6 datagram with an ICMPv6 message of T >= 8 transport bytes (type 128: an echo request), behind
+    a hop-by-hop header when `hbh`; the checksum over the pseudo header is valid unless bad_crc flips a bit."""
+    t = np.zeros(T, np.uint8)
+    t[8:] = rng.integers(0, 256, T - 8, dtype=np.uint8)
+    t[0] = icmp_type
+    t[4], t[5], t[6], t[7] = ident >> 8, ident & 0xFF, seq >> 8, seq & 0xFF
+    f = ipv6_datagram(rng, 58, t, src, dst, hbh)
+    c = _csum16_v6(f[8:24], f[24:40], 58, t)
+    f[f.size - T + 2], f[f.size - T + 3] = c >> 8, (c & 0xFF) ^ (0x10 if bad_crc else 0)
+    return f
+
+
+def udp6_datagram(rng, payload: int, sport: int = 4000, dport: int = 4001, src=None, dst=None) -> np.ndarray:
+    """One IPv6 datagram carrying UDP with `payload` random bytes and a valid checksum (a closed port's burst)."""
+    t = np.zeros(8 + payload, np.uint8)
+    t[0:6] = np.frombuffer(bytes([sport >> 8, sport & 0xFF, dport >> 8, dport & 0xFF, t.size >> 8, t.size & 0xFF]), np.uint8)
+    t[8:] = rng.integers(0, 256, payload, dtype=np.uint8)
+    f = ipv6_datagram(rng, 17, t, src, dst)
+    c = _csum16_v6(f[8:24], f[24:40], 17, t) or 0xFFFF
+    f[46], f[47] = c >> 8, c & 0xFF
+    return f
+
+
+def icmp6_answer_len(f, typ: int) -> int:
+    """The answer pico_icmp6_reply_batch_dev writes for datagram f with record type typ, taking f as well
+    formed: an echo's 40 + T behind 8 (hdr ext len + 1)-byte headers 0 / 43 / 60, a notice's 48 + min(40 +
+    len field, 1232)."""
+    plen = (int(f[4]) << 8 | int(f[5])) if len(f) >= 6 else 0
+    if typ != 0:
+        return 48 + min(40 + plen, 1232)
+    nx, o = int(f[6]) if len(f) >= 7 else 58, 40
+    while nx in (0, 43, 60) and o + 2 <= len(f):
+        nx, o = int(f[o]), o + 8 * (int(f[o + 1]) + 1)
+    return 40 + max(40 + plen - o, 0)
+
+
+def icmp6_burst(dgrams, types, codes=0, args=0, hop=64, seed: int = 101, align=0, slack=0, out_off=0, region=None,
+                local=bytes.fromhex("20010db8000000010000000000000001")):
+    """The inputs of pico_icmp6_reply_batch_dev for the datagrams `dgrams` (uint8 arrays, the IPv6 header
+    first): record i answers datagram i with types[i] (0: echo; 1 / 2 / 3 / 4: that notice, codes[i],
+    args[i]).  Laid out as icmp4_burst does: the datagrams in one buffer at `align` mod 16 each with `slack`
+    readable bytes behind (desc.len = bytes + slack; a negative slack cuts the descriptor short), the
+    answers' regions back to back at `out_off` mod 16 each, `region` bytes or -- None -- exactly the answer's
+    size (tight).  Returns (buffer, offsets uint64, lengths uint32, req records (src, arg, type, code, hop,
+    rsvd), out offsets uint64, out capacities uint32, out_len = 16 bytes past the last region)."""
+    n = len(dgrams)
+    bc = lambda x: np.broadcast_to(np.asarray(x, dtype=np.int64), (n,))
+    aligns, slacks, ooffs, cds, tps, ags, hops = bc(align), bc(slack), bc(out_off), bc(codes), bc(types), bc(args), bc(hop)
+    off, ln = np.zeros(n, np.uint64), np.zeros(n, np.uint32)
+    pos = 0
+    for i, f in enumerate(dgrams):
+        pos += (int(aligns[i]) - pos) % 16
+        off[i], ln[i] = pos, len(f) + int(slacks[i])
+        pos += len(f) + max(int(slacks[i]), 0)
+    buf = random_bytes(seed ^ 0x1C6F, pos)
+    for i, f in enumerate(dgrams):
+        buf[int(off[i]):int(off[i]) + len(f)] = f
+    req = np.zeros(n, np.dtype([("src", "u1", 16), ("arg", "<u4"), ("type", "u1"), ("code", "u1"), ("hop", "u1"), ("rsvd", "u1")]))
+    req["src"] = np.frombuffer(bytes(local), np.uint8)
+    req["arg"], req["type"], req["code"], req["hop"] = ags, tps, cds, hops
+    cap = np.array([icmp6_answer_len(f, int(tps[i])) if region is None else region for i, f in enumerate(dgrams)], np.uint32)
+    ooff = np.zeros(n, np.uint64)
+    pos = 0
+    for i in range(n):
+        pos += (int(ooffs[i]) - pos) % 16
+        ooff[i] = pos
+        pos += int(cap[i])
+    return buf, off, ln, req, ooff, cap, pos + 16
+
+
 def interleave_groups(desc, groups, seed: int = 91):
     """A seeded merge of group-contiguous frames into one arrival order that keeps each group's own order
     (what a link delivers when several flows send at once): desc = the frames' descriptors (any array
