@@ -62,7 +62,8 @@ extern "C" {
  *   4 (added, no bump): pico_tcp_ack_batch_dev and struct pico_csum_tcp_ack -- likewise;
  *   4 (added, no bump): pico_icmp4_reply_batch_dev, struct pico_csum_icmp4_req and struct
  *      pico_csum_icmp4_state -- likewise;
- *   4 (added, no bump): pico_icmp6_reply_batch_dev and struct pico_csum_icmp6_req -- likewise. */
+ *   4 (added, no bump): pico_icmp6_reply_batch_dev and struct pico_csum_icmp6_req -- likewise;
+ *   4 (added, no bump): pico_ipv6_fragment_batch_dev -- likewise. */
 #define PICO_CSUM_ABI_VERSION 4
 
 /* picoTCP pico_err values used here (include/pico_protocol.h:27,31,38 + ENODEV) */
@@ -433,6 +434,57 @@ int pico_ipv6_reassemble_batch_dev(const void *d_base, uint64_t base_len, const 
  * above.  d_out_frag, d_out_count, d_out_transport and d_verdict may each be NULL.  Regions and slot
  * ranges of different datagrams must not overlap.  One workgroup per datagram, one launch. */
 int pico_ipv4_fragment_batch_dev(const void *d_base, uint64_t base_len, const struct pico_csum_desc *d_dgram,
+                                 uint32_t n_dgram, uint32_t mtu, const uint32_t *d_groups, uint32_t n_frag, void *d_out,
+                                 uint64_t out_len, const struct pico_csum_desc *d_out_desc, uint32_t frag_stride,
+                                 struct pico_csum_desc *d_out_frag, uint32_t *d_out_count, uint16_t *d_out_transport,
+                                 uint8_t *d_verdict, uint32_t flags, void *stream);
+
+/* IPv6 TX fragmentation: the inverse of pico_ipv6_reassemble_batch_dev, fused with the transport
+ * checksum of the whole datagram -- mandatory for UDP over IPv6.  The reference has no sending side
+ * to mirror: pico_socket_xmit_fragments "Can't fragment IPv6" and cuts the datagram to one MTU
+ * (stack/pico_socket.c:1179-1185).  The split is RFC 8200 4.5's, and it is pinned to the reference's
+ * receiver: pico_ipv6_process_frag (modules/pico_fragments.c:432-498), compiled unmodified,
+ * reassembles the fragments written here into the datagram they were cut from
+ * (tests/golden/make_ref_fragtx6.py).  Everything not said here is as pico_ipv4_fragment_batch_dev
+ * states it.
+ *   d_dgram[]  one unfragmented datagram each: desc.off -> the 40-byte IPv6 fixed header followed
+ *              directly by the transport (no extension headers: an unfragmentable part is out of
+ *              scope), desc.len = 40 + T transport bytes, 40 <= len <= 65535 (what the IPv6 reassembly
+ *              batch accepts back), desc.seed = the 32-bit fragment identification in host order (the
+ *              host keeps the counter, as it keeps id for the segmentation batch).  The version nibble
+ *              (6), class and flow label, nxthdr, hop limit, src and dst are taken from the header;
+ *              its payload-length field is not read.  nxthdr names the transport: an extension
+ *              header's value (0, 43, 44, 50, 51, 60, 135) is MALFORMED.
+ *   split      per = (mtu - 48) & ~7 payload bytes a fragment (mtu >= 56, else -EINVAL; IPv6's minimum
+ *              of 1280 is the host's policy).  A datagram of desc.len <= mtu goes out whole, count 1:
+ *              its 40 header bytes with payload length = T and nxthdr unchanged, then the transport;
+ *              no fragment header; slot length = desc.len.  Else count = ceil(T / per), fragment k
+ *              carries transport bytes [k per, min((k + 1) per, T)) behind 48 header bytes: bytes 0-3
+ *              and 7-39 the template's, 4-5 = be16(8 + payload), 6 = 44, then the fragment header:
+ *              40 = the template's nxthdr, 41 = 0, 42-43 = be16(k per | 1 on every fragment but the
+ *              last), 44-47 = be32(seed).  d_out_frag[first + k] = {off + k frag_stride, 48 + payload, 0}.
+ *   d_out_desc[] as for IPv4; frag_stride a multiple of 4, >= 48 + per (else -EINVAL).  off = 0 mod
+ *              16 with a stride that is a multiple of 16 puts every payload on a 16-byte line.
+ *   d_groups[] as for IPv4.  A group that reserves exactly count slots lets d_out, d_out_frag and
+ *              d_groups go to pico_ipv6_reassemble_batch_dev as they are.  Its output header is then
+ *              fragment 0's (that batch's rule): nxthdr 44, payload length 8 + per -- a reassembled
+ *              datagram needs its byte 6 set by the host before it can be fragmented again.
+ *   d_out_transport[g] the value pico_ipv6_checksum_batch_dev reports with PICO_CSUM_F_TX for the same
+ *              datagram unfragmented: TCP (crc field at byte 16) / UDP (6) / ICMPv6 (2) over the
+ *              transport with the field read as zero and struct pico_ipv6_pseudo_hdr from the
+ *              template's addresses, T and nxthdr, stored as computed; 0 for any other protocol and
+ *              for a transport shorter than its header (20 / 8 / 4 bytes: that batch's MALFORMED,
+ *              here fragmented all the same).  With PICO_CSUM_F_WRITE a computed value is stored
+ *              into the fragment that holds the field: kf = crc_at / per, at byte 48 + crc_at -
+ *              kf per (a whole datagram: 40 + crc_at); without, the transport is copied verbatim.
+ *              Other flags: -EINVAL.
+ *   d_verdict[g]       ACCEPT, or MALFORMED = no byte of the region is written, count 0, slots
+ *              {0, 0, 0}: a datagram past base_len, len < 40 or > 65535, version not 6, an
+ *              extension-header nxthdr, fewer reserved slots than count, slots past n_frag (then no
+ *              slot is written either), a region too small for (count - 1) frag_stride + the last
+ *              fragment or past out_len.  Every check is made before the first store.
+ * Writes, reads, NULL outputs and overlap rules as for IPv4.  One workgroup per datagram, one launch. */
+int pico_ipv6_fragment_batch_dev(const void *d_base, uint64_t base_len, const struct pico_csum_desc *d_dgram,
                                  uint32_t n_dgram, uint32_t mtu, const uint32_t *d_groups, uint32_t n_frag, void *d_out,
                                  uint64_t out_len, const struct pico_csum_desc *d_out_desc, uint32_t frag_stride,
                                  struct pico_csum_desc *d_out_frag, uint32_t *d_out_count, uint16_t *d_out_transport,

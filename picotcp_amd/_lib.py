@@ -33,6 +33,7 @@ EXPORTED = (
     "pico_ipv4_reassemble_batch_dev",
     "pico_ipv6_reassemble_batch_dev",
     "pico_ipv4_fragment_batch_dev",
+    "pico_ipv6_fragment_batch_dev",
     "pico_tcp_segment_batch_dev",
     "pico_tcp_coalesce_batch_dev",
     "pico_tcp_ack_batch_dev",
@@ -116,6 +117,8 @@ def load() -> ctypes.CDLL:
     sig("pico_ipv4_reassemble_batch_dev", ctypes.c_int, vp, u64, vp, u32, vp, u32, vp, u64, vp, vp, vp, vp, vp)
     sig("pico_ipv6_reassemble_batch_dev", ctypes.c_int, vp, u64, vp, u32, vp, u32, vp, u64, vp, vp, vp, vp, u32, vp)
     sig("pico_ipv4_fragment_batch_dev", ctypes.c_int, vp, u64, vp, u32, u32, vp, u32, vp, u64, vp, u32, vp, vp, vp, vp, u32, vp)
+    if hasattr(lib, "pico_ipv6_fragment_batch_dev"):     # (an A/B build of an older round lacks it)
+        sig("pico_ipv6_fragment_batch_dev", ctypes.c_int, vp, u64, vp, u32, u32, vp, u32, vp, u64, vp, u32, vp, vp, vp, vp, u32, vp)
     sig("pico_tcp_segment_batch_dev", ctypes.c_int, vp, u64, vp, u32, vp, u32, vp, u64, vp, u32, vp, vp, vp, u32, vp)
     sig("pico_tcp_coalesce_batch_dev", ctypes.c_int, vp, u64, vp, u32, vp, vp, u32, vp, u64, vp, vp, vp, vp, u32, vp)
     if hasattr(lib, "pico_tcp_ack_batch_dev"):           # (likewise)

@@ -372,6 +372,34 @@ def ipv4_fragment_batch(base: torch.Tensor, dgram_desc: torch.Tensor, mtu: int, 
     return v, cnt, l4
 
 
+def ipv6_fragment_batch(base: torch.Tensor, dgram_desc: torch.Tensor, mtu: int, groups: torch.Tensor, n_frag: int,
+                        out: torch.Tensor, out_desc: torch.Tensor, frag_stride: int, flags: int = 0,
+                        out_frag: torch.Tensor | None = None, stream=None, results=None):
+    """IPv6 TX fragmentation scatter + the whole datagram's transport checksum (RFC 8200 4.5; the
+    reference cannot fragment IPv6, pico_socket.c:1179-1185, but reassembles what this writes,
+    pico_fragments.c:432-498): the inverse of ipv6_reassemble_batch.  As ipv4_fragment_batch, with
+    dgram_desc = one unfragmented datagram per descriptor (40-byte fixed header + transport, no
+    extension headers; seed = the 32-bit fragment identification), per = (mtu - 48) & ~7 payload
+    bytes behind 48 header bytes a fragment, frag_stride >= 48 + per; a datagram of len <= mtu goes
+    out whole, without a fragment header.  flags: F_WRITE stores the transport checksum into its crc
+    field.  Returns (verdict uint8[n], count int32[n], out_transport int16[n]); `results` may pass
+    that triple preallocated, any of them None to skip it."""
+    dev = _on_batch_device(base, dgram_desc=dgram_desc, groups=groups, out=out, out_desc=out_desc)
+    _require_u8(base, "base")
+    _require_u8(out, "out")
+    n = _pairs(groups, "groups")
+    _desc_bytes(dgram_desc, n, "dgram_desc")
+    _desc_bytes(out_desc, n, "out_desc")
+    _opt_desc_out(out_frag, n_frag, "out_frag", dev)
+    v, cnt, l4 = _results(results, _FRAGMENT_OUTS, (n, n, n), dev)
+    lib = _lib.load()
+    _lib.check("pico_ipv6_fragment_batch_dev",
+               lib.pico_ipv6_fragment_batch_dev(_ptr(base), base.numel(), _ptr(dgram_desc), n, mtu, _ptr(groups), n_frag,
+                                                _ptr(out), out.numel(), _ptr(out_desc), frag_stride, _ptr(out_frag),
+                                                _ptr(cnt), _ptr(l4), _ptr(v), flags, _stream_handle(stream)))
+    return v, cnt, l4
+
+
 def tcp_segment_batch(base: torch.Tensor, stream_desc: torch.Tensor, groups: torch.Tensor, n_seg: int,
                       out: torch.Tensor, out_desc: torch.Tensor, seg_stride: int, flags: int = 0,
                       out_seg: torch.Tensor | None = None, stream=None, results=None):

@@ -7,7 +7,7 @@
  * Layer 2: argument checking + launch-shape choice for the batched HIP
  *          kernels (pico_csum_k_raw.hip: uniform rings; pico_csum_k_sorted.hip:
  *          every descriptor batch and the forwarding step; pico_csum_k_frag.hip:
- *          reassembly; pico_csum_k_fragtx.hip: TX fragmentation; pico_csum_k_tcpseg.hip: TCP send
+ *          reassembly; pico_csum_k_fragtx.hip, pico_csum_k_fragtx6.hip: TX fragmentation; pico_csum_k_tcpseg.hip: TCP send
  *          segmentation; pico_csum_k_tcprx.hip: TCP receive coalescing; pico_csum_k_tcpack.hip: the burst's ACKs;
  *          pico_csum_k_icmp.hip: ICMPv4 answers, pico_csum_k_icmp6.hip: ICMPv6 answers), reached through the thin extern "C" launchers declared below.
  * Layer 3: host-resident batches: pinned staging, two streams, chunked
@@ -51,6 +51,10 @@ int pico_csum_launch_fragment(const void *base, uint64_t base_len, const void *d
                               const uint32_t *groups, uint32_t n_frag, void *out, uint64_t out_len, const void *out_desc,
                               uint32_t stride, void *o_frag, uint32_t *o_count, uint16_t *o_l4, uint8_t *verdict,
                               uint32_t flags, void *stream);
+int pico_csum_launch_fragment6(const void *base, uint64_t base_len, const void *dgram, uint32_t n_dgram, uint32_t mtu,
+                               const uint32_t *groups, uint32_t n_frag, void *out, uint64_t out_len, const void *out_desc,
+                               uint32_t stride, void *o_frag, uint32_t *o_count, uint16_t *o_l4, uint8_t *verdict,
+                               uint32_t flags, void *stream);
 int pico_csum_launch_tcp_segment(const void *base, uint64_t base_len, const void *strm, uint32_t n_stream,
                                  const uint32_t *groups, uint32_t n_seg, void *out, uint64_t out_len, const void *out_desc,
                                  uint32_t stride, void *o_seg, uint32_t *o_count, uint8_t *verdict, void *stream);
@@ -622,13 +626,16 @@ int pico_ipv6_reassemble_batch_dev(const void *d_base, uint64_t base_len, const 
                           d_out_len, d_out_transport, d_verdict, flags, stream, "pico_ipv6_reassemble_batch_dev");
 }
 
-int pico_ipv4_fragment_batch_dev(const void *d_base, uint64_t base_len, const struct pico_csum_desc *d_dgram,
-                                 uint32_t n_dgram, uint32_t mtu, const uint32_t *d_groups, uint32_t n_frag, void *d_out,
-                                 uint64_t out_len, const struct pico_csum_desc *d_out_desc, uint32_t frag_stride,
-                                 struct pico_csum_desc *d_out_frag, uint32_t *d_out_count, uint16_t *d_out_transport,
-                                 uint8_t *d_verdict, uint32_t flags, void *stream)
+/* the two TX fragmentation batches: hdr = the bytes in front of a fragment's payload (IPv4 20; IPv6 40 + the
+ * 8-byte fragment header), per = (mtu - hdr) & ~7 */
+static int fragment_dev(int v6, const void *d_base, uint64_t base_len, const struct pico_csum_desc *d_dgram,
+                        uint32_t n_dgram, uint32_t mtu, const uint32_t *d_groups, uint32_t n_frag, void *d_out,
+                        uint64_t out_len, const struct pico_csum_desc *d_out_desc, uint32_t frag_stride,
+                        struct pico_csum_desc *d_out_frag, uint32_t *d_out_count, uint16_t *d_out_transport,
+                        uint8_t *d_verdict, uint32_t flags, void *stream, const char *what)
 {
-    uint32_t per, min_stride;
+    const uint32_t hdr = v6 ? 48u : 20u;
+    uint32_t min_stride;
     int rc;
     if (n_dgram == 0)
         return 0;
@@ -640,18 +647,39 @@ int pico_ipv4_fragment_batch_dev(const void *d_base, uint64_t base_len, const st
         return fail(PICO_CSUM_EINVAL, "d_groups and d_out_count must be 4-byte, d_out_transport 2-byte aligned");
     if (flags & ~PICO_CSUM_F_WRITE)
         return fail(PICO_CSUM_EINVAL, "unknown flags 0x%x%s", flags, retired_note(flags));
-    if (mtu < 28u)
-        return fail(PICO_CSUM_EINVAL, "mtu %u: a fragment carries at least 8 payload bytes (mtu >= 28)", mtu);
-    per = (mtu - 20u) & ~7u;
-    min_stride = mtu < 20u + per ? mtu : 20u + per;
+    if (mtu < hdr + 8u)
+        return fail(PICO_CSUM_EINVAL, "mtu %u: a fragment carries at least 8 payload bytes (mtu >= %u)", mtu, hdr + 8u);
+    min_stride = hdr + ((mtu - hdr) & ~7u);
     if (frag_stride < min_stride || (frag_stride & 3u) != 0)
         return fail(PICO_CSUM_EINVAL, "frag_stride %u: a multiple of 4, at least %u", frag_stride, min_stride);
     if ((rc = need_device()) != 0)
         return rc;
-    return launch_status(pico_csum_launch_fragment(d_base, base_len, d_dgram, n_dgram, mtu, d_groups, n_frag, d_out,
-                                                   out_len, d_out_desc, frag_stride, d_out_frag, d_out_count,
-                                                   d_out_transport, d_verdict, flags, stream),
-                         "pico_ipv4_fragment_batch_dev");
+    return launch_status((v6 ? pico_csum_launch_fragment6 : pico_csum_launch_fragment)(
+                             d_base, base_len, d_dgram, n_dgram, mtu, d_groups, n_frag, d_out, out_len, d_out_desc,
+                             frag_stride, d_out_frag, d_out_count, d_out_transport, d_verdict, flags, stream),
+                         what);
+}
+
+int pico_ipv4_fragment_batch_dev(const void *d_base, uint64_t base_len, const struct pico_csum_desc *d_dgram,
+                                 uint32_t n_dgram, uint32_t mtu, const uint32_t *d_groups, uint32_t n_frag, void *d_out,
+                                 uint64_t out_len, const struct pico_csum_desc *d_out_desc, uint32_t frag_stride,
+                                 struct pico_csum_desc *d_out_frag, uint32_t *d_out_count, uint16_t *d_out_transport,
+                                 uint8_t *d_verdict, uint32_t flags, void *stream)
+{
+    return fragment_dev(0, d_base, base_len, d_dgram, n_dgram, mtu, d_groups, n_frag, d_out, out_len, d_out_desc,
+                        frag_stride, d_out_frag, d_out_count, d_out_transport, d_verdict, flags, stream,
+                        "pico_ipv4_fragment_batch_dev");
+}
+
+int pico_ipv6_fragment_batch_dev(const void *d_base, uint64_t base_len, const struct pico_csum_desc *d_dgram,
+                                 uint32_t n_dgram, uint32_t mtu, const uint32_t *d_groups, uint32_t n_frag, void *d_out,
+                                 uint64_t out_len, const struct pico_csum_desc *d_out_desc, uint32_t frag_stride,
+                                 struct pico_csum_desc *d_out_frag, uint32_t *d_out_count, uint16_t *d_out_transport,
+                                 uint8_t *d_verdict, uint32_t flags, void *stream)
+{
+    return fragment_dev(1, d_base, base_len, d_dgram, n_dgram, mtu, d_groups, n_frag, d_out, out_len, d_out_desc,
+                        frag_stride, d_out_frag, d_out_count, d_out_transport, d_verdict, flags, stream,
+                        "pico_ipv6_fragment_batch_dev");
 }
 
 int pico_tcp_segment_batch_dev(const void *d_base, uint64_t base_len, const struct pico_csum_desc *d_stream,

@@ -1,7 +1,8 @@
 // pico_csum_dev.h -- device helpers shared by the gfx950 kernel TUs of libpicocsum
 // (pico_csum_k_raw.hip, pico_csum_k_sorted.hip, pico_csum_k_frag.hip, pico_csum_k_fragtx.hip,
 // pico_csum_k_tcpseg.hip, pico_csum_k_tcprx.hip, pico_csum_k_tcpack.hip, pico_csum_k_icmp.hip,
-// pico_csum_k_icmp6.hip, pico_csum_k_flow.hip).
+// pico_csum_k_icmp6.hip, pico_csum_k_flow.hip, pico_csum_k_fragtx6.hip: the IPv6 form of _k_fragtx, which
+// uses what that one uses).
 // Header-only, internal; everything lives in an anonymous namespace (one copy per TU).
 // In order: the checksum arithmetic and the lane-group sums (every TU); windowed buffer loads
 // (_k_raw, _k_sorted, _k_frag); the IPv4 header rules (_k_sorted, _k_tcprx); the IPv6 extension-header
@@ -560,8 +561,8 @@ __device__ __forceinline__ uint32_t wave_total(uint32_t x) {
 //     differs from member to member.  Unit 0's load starts up to 15 bytes before the payload; the
 //     callers' payloads lie at least 20 bytes (K8: the IPv4 header), 24 bytes (K13: that and the
 //     ICMP header's first word), 16 bytes (K14's notices: the quote's first 16 bytes stay on the
-//     lanes; its echoes 48) or 40 bytes (K9, K10: network and TCP header) into their own readable
-//     buffer, so that is its byte 5 / 9 / 1 / 25 or later.
+//     lanes; its echoes 48) or 40 bytes (K9, K10: network and TCP header; K15: the IPv6 header) into
+//     their own readable buffer, so that is its byte 5 / 9 / 1 / 25 or later.
 //   * e = the end of the last 16-byte block that overlaps the member's readable buffer.  The whole-
 //     block read rule of include/pico_csum.h makes [.., e) readable and nothing behind it, so the
 //     one unit whose 16 bytes would run past e is read byte by byte, its [lo, hi) only.

@@ -498,6 +498,73 @@ def ipv4_oversized(lengths, mtu: int = 1500, stride: int = 1504, seed: int = 31,
     return buf, off, dlen.astype(np.uint32), groups, ooff, cap, int(reserved.sum()), pos + 16
 
 
+def fragtx6_count(length: int, mtu: int) -> int:
+    """Fragments pico_ipv6_fragment_batch_dev emits for a datagram of `length` bytes (the 40-byte
+    header included): 1 when it fits the MTU, else ceil(transport / per), per = (mtu - 48) & ~7."""
+    per = (mtu - 48) & ~7
+    return 1 if length <= mtu else -(-(length - 40) // per)
+
+
+def ipv6_oversized(lengths, mtu: int = 1500, stride: int = 1504, seed: int = 61, proto=17, align=0, out_off: int = 0,
+                   spare: int = 0, b9_proto: bool = False):
+    """Unfragmented IPv6 datagrams of the given TRANSPORT lengths (the 40-byte fixed header, no
+    extension headers, the payload-length field arbitrary: the fragmentation batch does not read
+    it) for pico_ipv6_fragment_batch_dev, with the arrays that place its output.  proto: one value or
+    one per datagram (6 / 17 / 58 get a plausible transport header with an arbitrary crc field);
+    align: the header's address mod 16 in the buffer, one value or one per datagram; b9_proto puts
+    proto into header byte 9 (the source address's second byte, which the reference's
+    pico_transport_crc_check dispatches on).  Output regions are laid out back to back, each
+    starting at out_off mod 16 and holding exactly the fragments at `stride`; every group reserves
+    its fragment count + `spare` slots.
+    Returns (buffer, dgram offsets uint64, dgram bytes uint32, ids uint32 (the descriptors' seed),
+    groups uint32[n, 2] = (first slot, slots reserved), out offsets uint64, out capacities uint32,
+    n_frag, out_len)."""
+    lengths = np.asarray(lengths, dtype=np.uint32)
+    n = lengths.size
+    protos = np.broadcast_to(np.asarray(proto, dtype=np.uint8), (n,))
+    aligns = np.broadcast_to(np.asarray(align, dtype=np.uint32), (n,))
+    rng = np.random.default_rng(seed)
+    per = (mtu - 48) & ~7
+    off = np.zeros(n, np.uint64)
+    pos = 0
+    pieces = []
+    for g, L in enumerate(lengths.tolist()):
+        pr = int(protos[g])
+        t = random_bytes(seed * 1000003 + g, L)
+        if pr == 6 and L >= 20:
+            t[12], t[13] = 0x50, 0x18
+        if pr == 17 and L >= 8:
+            t[4], t[5] = (L >> 8) & 0xFF, L & 0xFF
+        if pr == 58 and L >= 4:
+            t[0], t[1] = 128, 0
+        f = ipv6_datagram(rng, pr, t, hop=255 if pr == 58 else 64)
+        f[4:6] = rng.integers(0, 256, 2, dtype=np.uint8)
+        if b9_proto:
+            f[9] = pr
+        pos += (int(aligns[g]) - pos) % 16
+        off[g] = pos
+        pieces.append(f)
+        pos += 40 + L
+    buf = random_bytes(seed ^ 0x7F6A, pos + 16)
+    for g in range(n):
+        buf[int(off[g]):int(off[g]) + pieces[g].size] = pieces[g]
+    ids = rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
+    dlen = lengths + 40
+    cnt = np.array([fragtx6_count(int(x), mtu) for x in dlen.tolist()], np.uint32)
+    reserved = cnt + np.uint32(spare)
+    first = np.concatenate([[0], np.cumsum(reserved[:-1])]).astype(np.uint32)
+    groups = np.stack([first, reserved], axis=1).astype(np.uint32)
+    last = np.where(cnt == 1, dlen, 48 + (lengths - (cnt - 1) * per)).astype(np.int64)
+    cap = ((cnt.astype(np.int64) - 1) * stride + last).astype(np.uint32)
+    ooff = np.zeros(n, np.uint64)
+    pos = 0
+    for g in range(n):
+        pos += (out_off - pos) % 16
+        ooff[g] = pos
+        pos += int(cap[g])
+    return buf, off, dlen.astype(np.uint32), ids, groups, ooff, cap, int(reserved.sum()), pos + 16
+
+
 def tcpseg_count(payload: int, per: int) -> int:
     """Segments pico_tcp_segment_batch_dev emits for `payload` bytes at `per` bytes a segment:
     max(1, ceil(payload / per)) -- no payload is one bare-header frame."""
